@@ -21,14 +21,24 @@ launch queue are then in the state of a running stream, whatever K and W are (se
 
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the fused remap launch):
 algorithmic bytes per launch (3 B * (source + destination pixels), both eyes: SURVEY.md 8d)
-over its average duration: two events on the launch stream bracket the K timed steps.  `cpu_baseline` is the
-oracle (plain-C port of the reference path, oracle/) timed on this box's host cores on the same
-workload, rank 0 at N=1 only.  `roofline.traffic` is measured by this very run: rank 0 at N=1 runs
-two short `rocprofv3 --pmc` child passes of itself (FETCH_SIZE, WRITE_SIZE; separate passes, gfx950
-corrections of MI355X_MICROARCH.md) after the timed region; `traffic_source` says "live" or names
-the committed file it fell back to.  `cold` is what a first call costs (plan creation + first launch).
-`sustained` = a second leg of >= 1000 steps (>= 0.25 s) behind the timed region, bracketed the same way and NOT part of
-`value`: what a stream of frames sees, next to the driver's short window (`window_over_sustained` = their ratio).
+over its average duration: two events on the launch stream bracket the K timed steps.  `cold` is what
+the first step cost (plan creation + first launch).  Without --full, `roofline.traffic` is the committed
+figure of profiles/traffic_latest.json where that file holds the workload (`traffic_source` names it), else null.
+
+A plain run does only what the headline figure needs: set-up, conditioning, W warm-up steps, K timed steps,
+the outputs (--dump-outputs DIR) and the line.  `--full` adds, behind the timed region (rank 0 at N=1 unless said):
+`sustained` = a second leg of >= 1000 steps (>= 0.25 s), bracketed the same way and NOT part of `value`: what a stream
+of frames sees, next to the driver's short window (`window_over_sustained` = their ratio; every rank);
+`roofline.traffic` measured by this very run: two short `rocprofv3 --pmc` child passes of itself (FETCH_SIZE,
+WRITE_SIZE; separate passes, gfx950 corrections of MI355X_MICROARCH.md), `traffic_source` "live" or the committed
+file it fell back to, and for K x K workloads `roofline.valu_int` from a third pass; the cold cost of the 8192x8192
+Lanczos4 call and of radius="auto" (`cold_C4_8192_lanczos4`, `cold.new_radius_ms`); `cpu_baseline` = the oracle
+(plain-C port of the reference path, oracle/) timed on this box's host cores on the same workload, with
+`parity_vs_oracle` = the GPU result of buffer set 0 against it, byte for byte.
+
+`--dump-outputs DIR` writes what the last timed step returned (the SBS frame(s) / image of its buffer set) as
+float32 `DIR/<name>.npy`: whole when it fits DUMP_BUDGET_BYTES, else a fixed seeded sample of its elements (flat
+indices in `DIR/<name>_index.npy`, float64).  Inputs are seeded: the same arguments give the same arrays.
 """
 from __future__ import annotations
 
@@ -56,7 +66,10 @@ HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH
 ROTATE_MIN_BYTES = 640 << 20  # > 2x the 256 MiB Infinity Cache
 ROTATE_MIN_SETS = 3
 PMC_STEPS, PMC_WARMUP = 6, 2  # length of a rocprofv3 --pmc child pass
-SUSTAINED_MIN_STEPS = 1000  # the second, untimed-for-`value` leg of every run (`sustained` in the line)
+SUSTAINED_MIN_STEPS = 1000  # the second, untimed-for-`value` leg of a --full run (`sustained` in the line)
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files of a rank together
+DUMP_SAMPLES = 4 << 20  # elements of a sampled output (4 B value + 8 B index each: 48 MiB)
+DUMP_SEED = 20240619
 
 WORKLOADS = {
     # name: (eye size, transformer spec, interpolation)
@@ -459,6 +472,29 @@ def new_radius_cost(cfg, dev, V, transformer_builder):
     return out
 
 
+def dump_outputs(out_dir: Path, name: str, parts: list) -> None:
+    """--dump-outputs: the device tensors `parts` (one output, or the frames of a batch in order) as ONE float32 array
+    `<name>.npy` -- stacked whole if it fits the budget, else DUMP_SAMPLES elements at seeded flat indices of the
+    stacked array (sorted, in `<name>_index.npy` as float64; the same for every run of the same shape)."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    per = parts[0].numel()
+    assert all(p.numel() == per and p.is_contiguous() for p in parts)
+    total = per * len(parts)
+    if total * 4 <= DUMP_BUDGET_BYTES:
+        arr = torch.stack(parts) if len(parts) > 1 else parts[0]
+        np.save(out_dir / f"{name}.npy", arr.cpu().numpy().astype(np.float32))
+        return
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_SAMPLES, dtype=np.int64))
+    vals = []
+    for j, p in enumerate(parts):
+        lo, hi = np.searchsorted(idx, [j * per, (j + 1) * per])
+        if hi > lo:
+            sel = torch.from_numpy(idx[lo:hi] - j * per).to(p.device)
+            vals.append(p.reshape(-1)[sel].cpu().numpy())
+    np.save(out_dir / f"{name}.npy", np.concatenate(vals).astype(np.float32))
+    np.save(out_dir / f"{name}_index.npy", idx.astype(np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -482,9 +518,21 @@ def main() -> None:
                     help="skip the second, >= 1000-step leg behind the timed region (`sustained` in the line)")
     ap.add_argument("--no-condition", action="store_true",
                     help="skip the 0.5 s clock / launch-queue conditioning (the --pmc child passes: counters do not depend on clocks)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need (module docstring): the sustained leg, "
+                         "live rocprofv3 --pmc traffic / VALU passes, the extra cold calls, the CPU baseline and the parity check; "
+                         "the --no-* switches above and --traffic still leave out parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as float32 DIR/<name>.npy (a seeded sample of a large output)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.no_condition:  # (the counter passes: a few launches are all they need)
         args.no_sustained = True
+    if not args.full:  # a plain run: the headline figure and nothing else
+        args.no_sustained = args.no_cold_extra = args.no_cpu_baseline = True
+        if args.traffic == "live":
+            args.traffic = "file"
 
     PMC_CHILD_ARGS[:] = ["--split", args.split]
     rank = int(os.environ.get("RANK", "0"))
@@ -599,7 +647,7 @@ def main() -> None:
             ins = [noise_disc_torch(size, 2 * size, f + 100003 * k, dev, cn) for f in mine]
             outs = [torch.empty((size, 2 * size, cn), dtype=torch.uint8, device=dev) for _ in mine]
             sets.append(dict(srcs=[v for fr in ins for v in (fr[:, :size], fr[:, size:])],
-                             dsts=[v for fr in outs for v in (fr[:, :size], fr[:, size:])], sbs=outs[0]))
+                             dsts=[v for fr in outs for v in (fr[:, :size], fr[:, size:])], sbs=outs[0], outs=outs))
 
         def step(i: int):
             b = sets[i % nsets]
@@ -787,7 +835,7 @@ def main() -> None:
             else:
                 line["roofline"]["valu_int"] = {"source": "unmeasured (no rocprofv3 --pmc pass in this run)", "floor_ms": None, "frac_of_ceiling": None}
         if world == 1 and not child:
-            if not frames:
+            if not frames and not args.no_cpu_baseline:
                 torch.cuda.synchronize(dev)
                 gpu_out = sets[0]["sbs"].cpu().numpy()  # set 0 = the numpy-seeded pair (image)
             if args.traffic == "live":
@@ -817,6 +865,11 @@ def main() -> None:
                 line["cpu_baseline"] = cb
                 line["parity_vs_oracle"] = parity
         print(json.dumps(line), flush=True)
+    if args.dump_outputs:
+        # the buffer set the last timed step wrote (every later step of a --full run rewrites the same pixels from the same inputs)
+        last = sets[(args.warmup + args.steps - 1) % nsets]
+        name, parts = ("sbs_frames", last["outs"]) if frames else ("image" if single else "sbs", [last["sbs"]])
+        dump_outputs(Path(args.dump_outputs), name + (f"_rank{rank}" if world > 1 else ""), parts)
     if world > 1:
         dist.destroy_process_group()
 

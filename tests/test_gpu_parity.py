@@ -1569,7 +1569,8 @@ def test_bench_split_modes_rehearsal(split, workload):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     common = ["--workload", workload, "--split", split, "--steps", "3", "--warmup", "1", "--traffic", "none", "--no-cold-extra"]
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", *common], env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", *common, "--full"], env=env, capture_output=True, text=True,
+                       timeout=600)
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["parity_vs_oracle"]["bytes_differing"] == 0, line["parity_vs_oracle"]
     assert line["config"]["split"] == split and line["scaling"] == ("weak" if split == "frames" else "strong")

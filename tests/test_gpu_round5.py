@@ -488,7 +488,7 @@ def test_bench_lines_of_the_round5_workloads(workload, kinds):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--workload", workload, "--steps", "3", "--warmup", "1", "--traffic", "none",
-                        "--no-cold-extra", "--no-sustained"], env=env, capture_output=True, text=True, timeout=600)
+                        "--no-cold-extra", "--no-sustained", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert set(line["config"]["kernels"]) <= kinds, line["config"]["kernels"]

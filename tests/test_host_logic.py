@@ -263,3 +263,29 @@ def test_the_product_never_touches_the_oracle():
     for u in uses:  # every import sits inside a function whose name says cpu_baseline / parity check
         head = bench.rfind("\ndef ", 0, u)
         assert re.match(r"\ndef (cpu_baseline|_cpu_baseline|parity|_parity)", bench[head:head + 40]), bench[head:head + 60]
+
+
+def test_bench_dump_outputs_budget_and_sample(tmp_path):
+    """bench.py --dump-outputs: float32 arrays of at most 64 MB per run; a small output whole (a batch stacked in order), a large one as
+    the same seeded sample of element positions on every run, the values those positions hold."""
+    import torch
+
+    import bench
+
+    g = torch.Generator().manual_seed(1)
+    small = [torch.randint(0, 256, (24, 48, 3), dtype=torch.uint8, generator=g) for _ in range(3)]
+    bench.dump_outputs(tmp_path / "s", "sbs_frames", small)
+    got = np.load(tmp_path / "s" / "sbs_frames.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, torch.stack(small).numpy())
+    big = [torch.randint(0, 256, (1536, 3072, 3), dtype=torch.uint8, generator=g) for _ in range(2)]  # 2 x 14 M elements
+    for run in ("a", "b"):
+        bench.dump_outputs(tmp_path / run, "sbs_frames", big)
+    files = sorted((tmp_path / "a").iterdir())
+    assert [f.name for f in files] == ["sbs_frames.npy", "sbs_frames_index.npy"]
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    vals, idx = np.load(files[0]), np.load(files[1])
+    assert vals.dtype == np.float32 and idx.dtype == np.float64 and len(vals) == len(idx) > 1_000_000
+    assert np.array_equal(vals, torch.stack(big).numpy().reshape(-1)[idx.astype(np.int64)])
+    assert idx.min() < big[0].numel() <= idx.max()  # both frames sampled
+    for f in files:
+        assert np.array_equal(np.load(f), np.load(tmp_path / "b" / f.name))

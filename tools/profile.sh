@@ -7,7 +7,7 @@ TAG=${1:-r01}; shift || true
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python3 bench.py "$@" > $OUT/bench_line.json 2> $OUT/bench_stderr.log
+python3 bench.py --full "$@" > $OUT/bench_line.json 2> $OUT/bench_stderr.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 bench.py --no-cpu-baseline --traffic none --no-cold-extra "$@" > $OUT/bench_traced.log 2>&1
 find $OUT/trace -name '*kernel_stats.csv' | head -1 | xargs -I{} cp {} $OUT/kernel_stats.csv
 find $OUT/trace -name '*kernel_trace.csv' | head -1 | xargs -I{} sh -c 'head -1 {} > '$OUT'/kernel_trace_head.csv; grep -E "k_ray|k_remap|k_tile" {} | head -100 >> '$OUT'/kernel_trace_head.csv'
