@@ -289,3 +289,65 @@ def test_bench_dump_outputs_budget_and_sample(tmp_path):
     assert idx.min() < big[0].numel() <= idx.max()  # both frames sampled
     for f in files:
         assert np.array_equal(np.load(f), np.load(tmp_path / "b" / f.name))
+
+
+# chains that cannot be lowered (chain.NotLowerable): a polynomial longer than the op's parameter block, more stages than the op
+# list holds, a NormalizeTransformer with a tuple scale
+NOT_LOWERABLE = {
+    "poly17": [("equirect_enc", True), ("poly", [0.0, 1.0] + [0.0] * 14 + [-0.01]), CS.EQUI],
+    "stages17": [("equirect_enc", True)] + [("zoom", 1.0 + 0.001 * k) for k in range(1, 15)] + [CS.EQUI],
+}
+
+
+def _not_lowerable(name):
+    if name == "normalize_tuple_scale":
+        return T.EquirectangularEncoder() * T.NormalizeTransformer(center=(0.0, 0.0), scale=(1.0, 1.0)) * T.FisheyeDecoder("equidistant")
+    return CS.to_product(NOT_LOWERABLE[name])
+
+
+@pytest.mark.parametrize("name", [*NOT_LOWERABLE, "normalize_tuple_scale"])
+def test_auto_radius_declines_a_chain_that_cannot_be_lowered(name):
+    """radius="auto" on the device (remap_tensors_auto) must decline such a chain with NotImplementedError -- what both of its callers
+    (apply_lr_tensors' device form and the exact form's _remap_host_radius) catch to fall back to remap_tensors, whose LUT path serves
+    it from the chain's own transform().  NotLowerable escaped both, so the default apply_lr_tensors(t, L, R) raised.  The decision
+    precedes any device work: host tensors suffice."""
+    import torch
+
+    from vr180_convert_amd import remapper
+
+    t = _not_lowerable(name)
+    with pytest.raises(CH.NotLowerable):
+        CH.lower_for_get_map(t, radius=32.0, size_input=(64, 64), size_output=(48, 48))
+    srcs = [torch.zeros((64, 64, 3), dtype=torch.uint8) for _ in range(2)]
+    dsts = [torch.zeros((48, 48, 3), dtype=torch.uint8) for _ in range(2)]
+    for rad in (None, torch.tensor([[30.0, 0.0]], dtype=torch.float64)):
+        with pytest.raises(NotImplementedError, match="cannot be lowered"):
+            remapper.remap_tensors_auto(t, srcs, dsts, rad=rad, interpolation=1)
+
+
+@pytest.mark.parametrize("name", list(NOT_LOWERABLE))
+def test_host_map_of_a_chain_that_cannot_be_lowered_equals_the_numpy_oracle(name):
+    """What the LUT path remaps with: V.get_map of such a chain is the reference's own recipe through transform() (remapper.py:50-58),
+    equal to the oracle's NumPy evaluation of the same chain, float32 for float32."""
+    from oracle import chain_numpy
+
+    spec = NOT_LOWERABLE[name]
+    for r in (93.5, -120.0):
+        xm, ym = V.get_map(CS.to_product(spec), radius=r, size_input=(200, 240), size_output=(96, 80))
+        xw, yw = chain_numpy.get_map(spec, radius=r, size_input=(200, 240), size_output=(96, 80))
+        assert xm.dtype == np.float32 and xm.shape == (80, 96)
+        assert np.array_equal(xm, xw.astype(np.float32)) and np.array_equal(ym, yw.astype(np.float32))
+
+
+def test_auto_radius_groups_sources_by_shape():
+    """remap_tensors_auto makes one launch per source shape (a plan is made for one source size): the halves of an odd-width
+    side-by-side frame, or eyes of different heights, are two groups; equal shapes one -- host logic, first-appearance order."""
+    import torch
+
+    from vr180_convert_amd import remapper
+
+    sbs = torch.zeros((100, 401, 3), dtype=torch.uint8)
+    assert remapper.auto_groups([sbs[:, :200], sbs[:, 200:]]) == [((100, 200), [0]), ((100, 201), [1])]
+    assert remapper.auto_groups([sbs[:, :200], sbs[:, 201:]]) == [((100, 200), [0, 1])]
+    tall = torch.zeros((120, 200, 3), dtype=torch.uint8)
+    assert remapper.auto_groups([tall, sbs[:, :200], tall, sbs[:, 1:201]]) == [((120, 200), [0, 2]), ((100, 200), [1, 3])]

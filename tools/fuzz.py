@@ -308,7 +308,7 @@ def one_case(rng, dev, big: float) -> tuple[str, int]:
         V.remap_tensors(t, srcs, dsts, radius=radius, interpolation=interp, boarder_mode=border, boarder_value=bval, **kw)
         from vr180_convert_amd import remapper as _rm
 
-        if rng.random() < 0.12 and n <= 16 and len(_rm.last_launch_kinds()) == 1:
+        if rng.random() < 0.12 and n <= 16 and len(_rm.last_launch_kinds()) == 1 and _rm.last_launch_kinds() != ["lut"]:
             # the same launch recorded into a graph and replayed on restored destinations (plan_run is launch-only; a recorded launch
             # with a fix-up pass neither waits for nor records the plan's flag event)
             torch.cuda.synchronize()
@@ -512,8 +512,9 @@ def api_case(rng, dev) -> tuple[str, int]:
 
 def auto_case(rng, dev) -> tuple[str, int]:
     """radius='auto' with the radius never leaving the device (v1c_plan_run_auto; remapper.py:62-90 + :51-57): synthetic image
-    circles of random radius and offset, square-ish outputs, every interpolation, one transformer or one per eye -- against the
-    oracle's apply_lr(radius='auto'); where the device-resident form declines (fix-up pass needed) the exact one is compared."""
+    circles of random radius and offset, square-ish outputs, every interpolation (INTER_AREA included) and border mode, one
+    transformer or one per eye, eyes of one shape or the two halves of an odd-width side-by-side frame -- against the oracle's
+    apply_lr(radius='auto'); where the device-resident form declines (fix-up pass needed) the exact one is compared."""
     from vr180_convert_amd import remapper
 
     mid = []
@@ -523,8 +524,9 @@ def auto_case(rng, dev) -> tuple[str, int]:
         mid.insert(0, ("rot", rand_rot(rng, False).tolist()))
     spec = [("equirect_enc", True)] + mid + [("fisheye_dec", "equidistant" if rng.random() < 0.8 else MODELS[int(rng.integers(5))])]
     cn = int(rng.choice([3, 3, 3, 1, 4]))
-    interp = int(rng.choice([4, 4, 1, 1, 0, 2]))
-    border = int(rng.choice([0, 0, 0, 1, 4]))
+    interp = int(rng.choice([4, 4, 1, 1, 0, 2, 3]))
+    border = int(rng.choice([0, 0, 0, 1, 2, 3, 4, 5]))
+    bv = tuple(int(v) for v in rng.integers(0, 256, 4)) if rng.random() < 0.5 else 0
     hs, ws = int(rng.integers(64, 900)), int(rng.integers(64, 900))
     if rng.random() < 0.6:
         ws = (ws + 3) & ~3
@@ -532,33 +534,44 @@ def auto_case(rng, dev) -> tuple[str, int]:
     ho = wo if rng.random() < 0.7 else max(16, wo + int(rng.integers(-80, 80)))
     tuple_t = rng.random() < 0.25
 
-    def disc():
-        im = rng.integers(30, 256, (hs, ws, cn), dtype=np.uint8)
-        yy, xx = np.mgrid[:hs, :ws]
-        r = min(hs, ws) * float(rng.uniform(0.25, 0.52))
-        cx, cy = ws / 2 + float(rng.uniform(-4, 4)), hs / 2 + float(rng.uniform(-4, 4))
+    def disc(w):
+        im = rng.integers(30, 256, (hs, w, cn), dtype=np.uint8)
+        yy, xx = np.mgrid[:hs, :w]
+        r = min(hs, w) * float(rng.uniform(0.25, 0.52))
+        cx, cy = w / 2 + float(rng.uniform(-4, 4)), hs / 2 + float(rng.uniform(-4, 4))
         im[((xx - cx) ** 2 + (yy - cy) ** 2) > r * r] = 0
         return im
 
-    a, b = disc(), disc()
-    desc = f"AUTO spec={spec!r} cn={cn} interp={interp} border={border} out=({wo},{ho}) src=({ws},{hs}) tuple={tuple_t}"
+    if rng.random() < 0.2:  # the two halves of an odd-width side-by-side frame: W // 2 and W - W // 2 columns of one tensor
+        wsbs = 2 * ws + 1
+        frame = np.concatenate([disc(wsbs // 2), disc(wsbs - wsbs // 2)], axis=1)
+        a, b = frame[:, : wsbs // 2], frame[:, wsbs // 2 :]
+        fd = torch.from_numpy(frame).to(dev)
+        la, lb = fd[:, : wsbs // 2], fd[:, wsbs // 2 :]
+    else:
+        a, b = disc(ws), disc(ws)
+        la, lb = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
+    desc = (f"AUTO spec={spec!r} cn={cn} interp={interp} border={border} bv={bv} out=({wo},{ho}) src=({a.shape[1]}|{b.shape[1]},{hs}) "
+            f"tuple={tuple_t}")
     try:
         ra, rb = O.get_radius(a), O.get_radius(b)
     except IndexError:
         return desc + " (no black border: skipped)", 0
     t = CS.to_product(spec)
     tt = (t, t) if tuple_t else t
-    sbs = V.apply_lr_tensors(tt, torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev), size_output=(wo, ho), interpolation=interp,
-                             boarder_mode=border, radius="auto", auto_radius_on_device=True)
+    sbs = V.apply_lr_tensors(tt, la, lb, size_output=(wo, ho), interpolation=interp, boarder_mode=border, boarder_value=bv, radius="auto",
+                             auto_radius_on_device=True)
     form = remapper.last_auto_radius_form()
     KINDS["auto:" + form] = KINDS.get("auto:" + form, 0) + 1
     got = sbs.cpu().numpy()
     bad = 0
     for k, (im, r_used) in enumerate(((a, ra if tuple_t else max(ra, rb)), (b, rb if tuple_t else max(ra, rb)))):
-        xm, ym = O.get_map(spec, radius=r_used, size_input=(hs, ws), size_output=(wo, ho))
-        want = O.remap(im, xm, ym, interp, border, 0)
+        # (one shared transformer: images[0]'s geometry for both eyes, remapper.py:385; per-eye transformers: each its own)
+        size_in = (hs, int(im.shape[1])) if tuple_t else (hs, int(a.shape[1]))
+        xm, ym = O.get_map(spec, radius=r_used, size_input=size_in, size_output=(wo, ho))
+        want = O.remap(im, xm, ym, interp, border, bv)
         g = got[:, k * wo:(k + 1) * wo]
-        sing = ill_conditioned(spec, r_used, (hs, ws), (wo, ho))
+        sing = ill_conditioned(spec, r_used, size_in, (wo, ho))
         if border in (1, 2, 3, 4):
             sing |= ~((np.abs(xm) < 2.0 ** 20) & (np.abs(ym) < 2.0 ** 20))
         d = (g != want).any(axis=2)

@@ -1085,6 +1085,10 @@ static int run_auto(v1c_plan* p, void* stream, const v1c_unit* units, int n_unit
         return fail(V1C_E_UNSUPPORTED, "v1c_plan_run_auto: at most 16 units per call");
     if (p->mode != MODE_RAY || p->gen_mode != 0 || p->ana.base != 0 || p->n_rot_stages > 1 || p->disable_fast)
         return fail(V1C_E_UNSUPPORTED, "v1c_plan_run_auto: chains of the form EquirectangularEncoder() * [one rotation] * radial stages only");
+    // (the patch kernels write the scale (r, r): get_map's DenormalizeTransformer(scale=(radius, radius)), remapper.py:55 -- a plan made
+    //  from an anisotropic Denormalize would have its rx / ry replaced silently)
+    if (p->ctx.ray.rx != p->ctx.ray.ry)
+        return fail(V1C_E_UNSUPPORTED, "v1c_plan_run_auto: the plan's Denormalize scale must be isotropic (rx == ry)");
     DeviceGuard dg(p->device);
     if (!dg.ok)
         return fail(V1C_E_NODEVICE, "hipSetDevice failed");

@@ -225,16 +225,26 @@ _AUTO_LAST: dict = {}  # (chain, geometry) -> the radius its last radius="auto" 
 _TLS = threading.local()  # .plans: the plans the calling thread's last remap_tensors ran (last_launch_kinds)
 
 
+class _LutLaunch:
+    """A unit remapped from a host-computed map (``v1c_remap_lut``: chains that cannot be lowered), as ``last_launch_kinds`` reports it."""
+
+    @staticmethod
+    def last_launch() -> str:
+        return "lut"
+
+
 def last_launch_kinds() -> list[str]:
     """Kernel family per launch group of the calling thread's most recent ``remap_tensors`` / ``apply_lr_tensors`` call
-    (``Plan.last_launch``: 'generic', 'tile', 'mirror', 'batch', 'rot_pair', 'cn', 'cn_rot', '+fixup' appended when a fix-up pass followed).  The engine
-    serves the same bytes through several kernels; tests use this to make sure a case meant for a tiled kernel reached it."""
+    (``Plan.last_launch``: 'generic', 'tile', 'mirror', 'batch', 'rot_pair', 'cn', 'cn_rot', '+fixup' appended when a fix-up pass followed;
+    'lut' per unit whose map came from the chain's own ``transform()``).  The engine serves the same bytes through several kernels; tests
+    use this to make sure a case meant for a tiled kernel reached it."""
     return [p.last_launch() for p in getattr(_TLS, "plans", [])]
 
 
 def last_auto_radius_form() -> str:
-    """Which form the calling thread's most recent ``apply_lr_tensors(radius="auto")`` took: 'device' (``remap_tensors_auto``: the radius
-    never left the GPU) or 'exact' (estimates brought to the host); '' before the first such call.  For tests and the bench."""
+    """Which form the calling thread's most recent ``apply_lr_tensors(radius="auto")`` (or successful ``remap_tensors_auto``) took: 'device'
+    (``remap_tensors_auto``: the radius never left the GPU) or 'exact' (estimates brought to the host); '' before the first such call.
+    For tests and the bench."""
     return getattr(_TLS, "auto_form", "")
 
 
@@ -449,6 +459,7 @@ def remap_tensors(
         if memo_key is not None and len(groups) == 1 and not host_mapped and g.rots is None and len(g.srcs) == n:
             plan.path_cached = paths[-1]
             _LAST_SHARED[0] = (memo_key, plan)
+    _TLS.plans.extend([_LutLaunch] * len(host_mapped))  # (after the plans' groups: a LUT unit reports 'lut')
     return paths
 
 
@@ -683,8 +694,14 @@ def remap_tensors_auto(transformer: TransformerBase, srcs: Sequence[torch.Tensor
     estimated from ``srcs`` (or given as ``rad``, ``auto_radius_tensor``), the maximum taken and the Denormalize scale set by ONE small
     launch in front of the remap launch (``v1c_plan_run_auto_images`` / ``v1c_plan_run_auto``).  No stream synchronisation, no
     plan per image (ONE plan serves every radius: it is keyed on the nominal radius "max"), graph-capturable once the plan exists.
-    Where the reference raises IndexError (an image without a black border) the output is the border colour.
-    Raises NotImplementedError for chains the device-resident form does not serve (see include/vr180_remap.h)."""
+    Where the reference raises IndexError (an image without a black border) the map is sent to the Denormalize centre -40000 px
+    (scale 0): every pixel samples there under the border mode -- BORDER_CONSTANT the border colour, BORDER_TRANSPARENT leaves ``dsts``
+    untouched, REPLICATE / REFLECT / WRAP / REFLECT_101 what those modes read at (-40000, -40000).
+    Sources of different shapes (the halves of an odd-width side-by-side frame) share the map of ``srcs[0]``'s geometry, like
+    ``remap_tensors``: one radius over all of them (``auto_radius_tensor``), one launch per source shape (``auto_groups``).
+    Raises NotImplementedError for chains the device-resident form does not serve (see include/vr180_remap.h), chains that cannot be
+    lowered among them; a decline after the first of several shape groups has run leaves that group's outputs written (with the very
+    bytes the caller's fallback writes again)."""
     if isinstance(transformer, (list, tuple)):
         raise ValueError("remap_tensors_auto takes ONE transformer (per-eye transformers: one call per eye, as apply_lr does)")
     dev = srcs[0].device
@@ -692,11 +709,31 @@ def remap_tensors_auto(transformer: TransformerBase, srcs: Sequence[torch.Tensor
     dst_wh = (int(dsts[0].shape[1]), int(dsts[0].shape[0]))
     size_in = tuple(size_input) if size_input is not None else src_hw
     nominal = min(size_in[0] / 2, size_in[1] / 2)  # (any radius: the launch ignores the plan's own)
-    chain = _lower_cached(transformer, radius=nominal, size_input=size_in, size_output=dst_wh)
-    plan = _plan_for(chain, src_hw=src_hw, dst_wh=dst_wh, cn=int(srcs[0].shape[2]), interpolation=interpolation,
-                     border_mode=boarder_mode, border_value=boarder_value, device=dev)
-    plan.run_auto(srcs, dsts, rad)  # (rad None: the call estimates from `srcs` itself -- one small launch in front of the remap)
-    _TLS.plans = [plan]
+    try:
+        chain = _lower_cached(transformer, radius=nominal, size_input=size_in, size_output=dst_wh)
+    except NotLowerable as e:  # (the callers' fallback, remap_tensors, serves it from the chain's own transform(): the LUT path)
+        raise NotImplementedError(f"remap_tensors_auto: the chain cannot be lowered ({e})") from e
+    groups = auto_groups(srcs)
+    if len(groups) > 1 and rad is None:
+        rad = auto_radius_tensor(srcs)  # (ONE radius over every source: the scan launch of run_auto only sees its own group)
+    plans = []
+    for hw, idx in groups:
+        plan = _plan_for(chain, src_hw=hw, dst_wh=dst_wh, cn=int(srcs[0].shape[2]), interpolation=interpolation,
+                         border_mode=boarder_mode, border_value=boarder_value, device=dev)
+        # (rad None: the call estimates from `srcs` itself -- one small launch in front of the remap)
+        plan.run_auto([srcs[k] for k in idx], [dsts[k] for k in idx], rad)
+        plans.append(plan)
+    _TLS.plans = plans
+    _TLS.auto_form = "device"
+
+
+def auto_groups(srcs: Sequence[Any]) -> list[tuple[tuple[int, int], list[int]]]:
+    """How ``remap_tensors_auto`` splits its units: ``(source (H, W), unit indices)`` per distinct source shape, in first-appearance
+    order (a ``v1c_plan`` is made for one source size).  Host logic only: shapes are read, no device is touched."""
+    acc: "OrderedDict[tuple[int, int], list[int]]" = OrderedDict()
+    for k, s in enumerate(srcs):
+        acc.setdefault((int(s.shape[0]), int(s.shape[1])), []).append(k)
+    return list(acc.items())
 
 
 def _remap_host_radius(transformer: TransformerBase, srcs, dsts, r: float, *, interpolation, boarder_mode, boarder_value, size_input) -> bool:
@@ -722,6 +759,7 @@ def _remap_host_radius(transformer: TransformerBase, srcs, dsts, r: float, *, in
         rad = torch.tensor([[r, 0.0]], dtype=torch.float64, device=dev)
         remap_tensors_auto(transformer, srcs, dsts, rad=rad, interpolation=interpolation, boarder_mode=boarder_mode, boarder_value=boarder_value,
                            size_input=size_input)
+        _TLS.auto_form = "exact"  # (the estimate did visit the host)
         return True
     except NotImplementedError:
         return False
