@@ -169,6 +169,23 @@ const char* v1c_last_error(void);
 int v1c_plan_create(v1c_plan** out, int device, const v1c_chain* chain,
                     int src_h, int src_w, int dst_h, int dst_w, int cn,
                     int interp, int border_mode, const uint8_t border_val[4]);
+
+/* ---- pixel types: cv2 depth codes -----------------------------------------------------
+ * The reference hands whatever array it has to cv2.remap (remapper.py:366-378, 448-456), which takes CV_16U and CV_32F images as well
+ * as 8-bit ones: 16-bit TIFF / PNG from RAW development, linear-light float32.  Every entry point without `_ex` is 8-bit.       */
+#define V1C_DEPTH_8U  0
+#define V1C_DEPTH_16U 2
+#define V1C_DEPTH_32F 5
+
+/* v1c_plan_create for any of the depths above.  `border_val` is cv2's Scalar of doubles (NULL = 0), saturated to the pixel type
+ * inside (cvRound half to even and [0, 255] / [0, 65535] for 8U / 16U, (float) for 32F).  With V1C_DEPTH_8U it is exactly the plan
+ * v1c_plan_create makes.  Plans of a wide depth (16U, 32F) take units whose pointers and pitches are multiples of the pixel type's
+ * size, pitches in BYTES (>= w * cn * sizeof); v1c_plan_run serves them through k_remap_wide (V1C_LAUNCH_WIDE, | V1C_LAUNCH_FIXUP
+ * behind a fix-up pass), v1c_plan_run_auto / _auto_images return V1C_E_UNSUPPORTED (take the radius to the host), v1c_plan_get_map
+ * works as for every plan.  Arithmetic: INTEGRATION.md, "16-bit and float32 images" (cv2's float-weight remap, restated).       */
+int v1c_plan_create_ex(v1c_plan** out, int device, const v1c_chain* chain, int src_h, int src_w,
+                       int dst_h, int dst_w, int cn, int depth, int interp, int border_mode,
+                       const double border_val[4]);
 int v1c_plan_destroy(v1c_plan* plan);
 
 /* Which device code path the plan selected: 0 = generic fp64 interpreter, 1 = fused
@@ -228,6 +245,7 @@ enum {
     V1C_LAUNCH_CN_ROT = 4,  /* grayscale / BGRA, units with a rotation of their own: k_ray_lin_cn without boxes */
     V1C_LAUNCH_BATCH = 5,   /* BGR bilinear batches sharing a map: k_ray_lin3_batch_lean_raw (+ k_ray_lin3_tile for its rest tiles) */
     V1C_LAUNCH_ROT_PAIR = 6, /* BGR bilinear units with a rotation of their own: k_ray_lin3_rot_pair_raw */
+    V1C_LAUNCH_WIDE = 7,    /* 16-bit / float32 pixels: k_remap_wide (plans of v1c_plan_create_ex with a wide depth) */
     V1C_LAUNCH_FIXUP = 0x100
 };
 int v1c_plan_last_launch(const v1c_plan* plan);
@@ -259,6 +277,13 @@ int v1c_remap_lut(int device, void* stream,
                   const float* xmap, const float* ymap, int64_t map_pitch,
                   int interp, int border_mode, const uint8_t border_val[4]);
 
+/* v1c_remap_lut for any depth (V1C_DEPTH_*): pitches in bytes, `border_val` a cv2 Scalar of doubles as in v1c_plan_create_ex.
+ * Wide depths need pointers and pitches that are multiples of the pixel type's size.                                         */
+int v1c_remap_lut_ex(int device, void* stream, const void* src, int src_h, int src_w, int64_t src_pitch,
+                     int cn, int depth, void* dst, int dst_h, int dst_w, int64_t dst_pitch,
+                     const float* xmap, const float* ymap, int64_t map_pitch,
+                     int interp, int border_mode, const double border_val[4]);
+
 /* Auto-radius estimate of one device-resident image, get_radius() transformer.py:108-140
  * (centre row / column scan on the device, threshold on the channel mean, sign quirk preserved).
  * Synchronous: returns the value through *radius.  Returns V1C_E_INVALID with the message
@@ -286,6 +311,11 @@ int v1c_anaglyph(int device, void* stream,
  * (SURVEY.md Appendix A item 3).  Host-only (no device needed); `out` is a HOST buffer.
  * Lets callers and tests inspect exactly what the kernels read.                            */
 int v1c_build_itab(int interp, int16_t* out);
+
+/* The float32 weight table of the 16-bit / float32 sampler: wf[fy*32+fx][ky][kx] = t1d[fy][ky] * t1d[fx][kx] with OpenCV's 1-D
+ * weights t1d (the ones v1c_build_itab rounds; LINEAR: {1 - k/32, k/32}) and no sum fix-up.  INTER_LINEAR (1024*2*2 entries),
+ * INTER_CUBIC (1024*4*4) or INTER_LANCZOS4 (1024*8*8).  Host-only; `out` is a HOST buffer.                                 */
+int v1c_build_ftab(int interp, float* out);
 
 #ifdef __cplusplus
 }

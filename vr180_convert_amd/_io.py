@@ -3,10 +3,13 @@
 BGR like cv2's.  Codec work is outside the measured path.
 
 Two additions for batch work, where codecs -- not the remap -- set the end-to-end time:
-* ``.npy`` files are read (memory-mapped) and written as raw uint8 arrays in cv2 channel order: the codec-free
+* ``.npy`` files are read (memory-mapped) as raw uint8 arrays and written as raw uint8 / uint16 / float32 arrays (anything else
+  saturated to uint8, as before) in cv2 channel order: the codec-free
   format for frame sequences (the GPU image ships no device-side JPEG / PNG codec: no rocJPEG, no torchvision);
 * large PNGs are written by the multi-threaded encoder of ``_png.py`` when cv2 is absent, and PNGs it wrote are read back by its
-  multi-threaded decoder (a private chunk holds the band directory; every other reader sees an ordinary PNG)."""
+  multi-threaded decoder (a private chunk holds the band directory; every other reader sees an ordinary PNG);
+* uint16 results written to ``.png`` become 16-bit PNGs, as with cv2.imwrite; float32 results and other formats are saturated to
+  8 bits like cv2.imwrite does."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -52,13 +55,24 @@ def imread(path: Any):
 
 def imwrite(path: Any, image: np.ndarray) -> bool:
     p = Path(path).as_posix()
-    if image.dtype != np.uint8:
+    ext = Path(p).suffix.lower()
+    if ext == ".npy" and image.dtype in (np.uint16, np.float32):  # (the remap's wide pixel types, as they are)
+        np.save(p, np.ascontiguousarray(image))
+        return True
+    png16 = ext == ".png" and image.dtype == np.uint16 and image.ndim in (2, 3)  # cv2.imwrite writes a 16-bit PNG of a uint16 image
+    if image.dtype != np.uint8 and not png16:
         image = np.clip(np.rint(image), 0, 255).astype(np.uint8)  # cv2.imwrite converts with saturation
-    if p.lower().endswith(".npy"):
+    if ext == ".npy":
         np.save(p, np.ascontiguousarray(image))
         return True
     if _cv is not None:
         return bool(_cv.imwrite(p, image))
+    if png16:
+        # (Pillow cannot write 16-bit RGB: this package's encoder, at any size)
+        from . import _png
+
+        _png.write(p, image, level=1)
+        return True
     if p.lower().endswith(".png") and image.size >= PARALLEL_PNG_MIN_BYTES and image.ndim in (2, 3):
         from . import _png
 
@@ -68,7 +82,6 @@ def imwrite(path: Any, image: np.ndarray) -> bool:
 
     arr = image if image.ndim == 2 else image[..., ::-1] if image.shape[2] == 3 else image[..., [2, 1, 0, 3]]
     # cv2.imwrite's defaults: PNG compression level 1 (IMWRITE_PNG_COMPRESSION), JPEG quality 95
-    ext = Path(p).suffix.lower()
     opts = {"compress_level": 1} if ext == ".png" else {"quality": 95} if ext in (".jpg", ".jpeg") else {}
     Image.fromarray(np.ascontiguousarray(arr)).save(p, **opts)
     return True

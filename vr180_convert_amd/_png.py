@@ -58,20 +58,23 @@ def _to_png_order(dst: np.ndarray, a: np.ndarray) -> None:
 
 
 def encode(image: np.ndarray, *, level: int = 1, threads: int | None = None, band_rows: int | None = None, up_filter: bool = True) -> bytes:
-    """PNG bytes of a uint8 image in cv2 channel order: (H, W) gray, (H, W, 3) BGR or (H, W, 4) BGRA.
+    """PNG bytes of a uint8 or uint16 image in cv2 channel order: (H, W) gray, (H, W, 3) BGR or (H, W, 4) BGRA; uint16 gives
+    bit depth 16 (big-endian samples, like cv2.imwrite).
     ``up_filter``: scanline filter 2 ("Up": each byte minus the one above it, one vectorised subtraction) instead
     of 0 ("None") -- photographs deflate about a third smaller and faster."""
-    if image.dtype != np.uint8 or image.ndim not in (2, 3):
-        raise TypeError("PNG encoder takes uint8 (H, W[, C]) arrays")
+    if image.dtype not in (np.uint8, np.uint16) or image.ndim not in (2, 3):
+        raise TypeError("PNG encoder takes uint8 / uint16 (H, W[, C]) arrays")
     a = image if image.ndim == 3 else image[..., None]
     h, w, cn = a.shape
     if cn not in (1, 3, 4) or h == 0 or w == 0:
         raise ValueError("1, 3 or 4 channels and a non-empty image")
     color_type = {1: 0, 3: 2, 4: 6}[cn]
+    nb = a.dtype.itemsize  # bytes per sample: the filters work on bytes whatever the depth
+    sample = np.dtype(">u2") if nb == 2 else np.dtype(np.uint8)
     nthreads = threads or min(32, os.cpu_count() or 1)
     rows = band_rows or max(16, -(-h // (4 * nthreads)))
     bands = [(r, min(r + rows, h)) for r in range(0, h, rows)]
-    stride = 1 + w * cn
+    stride = 1 + w * cn * nb
 
     def band(k: int):
         # everything a band needs on its own thread (numpy and zlib release the GIL): scanlines = filter byte + pixels in RGB(A)
@@ -80,16 +83,16 @@ def encode(image: np.ndarray, *, level: int = 1, threads: int | None = None, ban
         r0, r1 = bands[k]
         lines = np.empty((r1 - r0, stride), np.uint8)
         lines[:, 0] = 2 if up_filter else 0
-        body = lines[:, 1:].reshape(r1 - r0, w, cn)
+        body = lines[:, 1:].view(sample).reshape(r1 - r0, w, cn)
         _to_png_order(body, a[r0:r1])
         if up_filter:
             flat = lines[:, 1:]
             if r1 - r0 > 1:
                 flat[1:] -= flat[:-1].copy()
             if r0 > 0:
-                above = np.empty((1, w, cn), np.uint8)
+                above = np.empty((1, w, cn), sample)
                 _to_png_order(above, a[r0 - 1:r0])
-                flat[0] -= above.reshape(-1)
+                flat[0] -= above.view(np.uint8).reshape(-1)
         c = zlib.compressobj(level, zlib.DEFLATED, -15)
         part = c.compress(lines) + c.flush(zlib.Z_FINISH if k == len(bands) - 1 else zlib.Z_SYNC_FLUSH)
         return part, zlib.adler32(lines), lines.size
@@ -104,7 +107,7 @@ def encode(image: np.ndarray, *, level: int = 1, threads: int | None = None, ban
     for _, ad, n in done:
         adler = _adler32_combine(adler, ad, n)
     stream = b"\x78\x01" + b"".join(parts) + struct.pack(">I", adler & 0xFFFFFFFF)
-    ihdr = struct.pack(">IIBBBBB", w, h, 8, color_type, 0, 0, 0)
+    ihdr = struct.pack(">IIBBBBB", w, h, 8 * nb, color_type, 0, 0, 0)
     # band directory for decode(): an ancillary, private, unsafe-to-copy chunk other readers skip.  Every band was deflated from an
     # empty window, so each segment inflates on its own.
     index = struct.pack(">BBI", 1, 2 if up_filter else 0, len(bands))

@@ -79,6 +79,17 @@ hipError_t launch_remap(int mode, const KernelCtx& c, const UnitArgs& ua, int n_
 hipError_t launch_get_map(int mode, const KernelCtx& c, const UnitArgs& u, float* xmap, float* ymap, int64_t pitch,
                           hipStream_t stream);
 
+// ---- 16-bit / float32 pixels (kernels_wide.hip: k_remap_wide) ----
+// The wide kernels' own argument, behind KernelCtx and UnitArgs (whose layouts the uint8 kernels keep): the saturated border colour
+// (cv2's Scalar, saturate_cast to the pixel type, held as float: exact for 16U) and the float weight table of CUBIC / LANCZOS4
+// (build_ftab, plan.hip; null for NEAREST / LINEAR, whose weights are formed in the sampler).
+struct WideArgs {
+    const float* ftab;
+    float cval[4];
+};
+// `depth`: V1C_DEPTH_16U or V1C_DEPTH_32F; `mode`: MODE_LITERAL / MODE_RAY / MODE_FIXUP / MODE_LUT as launch_remap
+hipError_t launch_remap_wide(int mode, int depth, const KernelCtx& c, const UnitArgs& ua, const WideArgs& wa, int n_units, hipStream_t stream);
+
 // ---- tile kernels (kernels_tile.hip, kernels_mirror.hip, kernels_cn.hip; building blocks in tile_device.hpp).  Every launcher takes the plan's context twice -- `c`, the host copy its decisions read, and
 // `cdev`, the device copy the kernels read --, the launch's units and `flags`: the plan's tile-flag words when a fix-up pass follows
 // the launch, null when the host has proven it unnecessary (the kernels then write none). ----

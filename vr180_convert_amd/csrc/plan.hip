@@ -155,6 +155,59 @@ extern "C" int v1c_build_itab(int interp, int16_t* out)
     return V1C_OK;
 }
 
+// The float32 table of the 16-bit / float32 sampler (v1c_core.hpp: sample_wide): the products build_itab rounds to int16, kept as
+// they are -- remapBicubic / remapLanczos4 instantiated with float weights use initInterTab2D's float table, which has no sum
+// fix-up.  LINEAR: t1d = {1 - k/32, k/32} (the kernels form these exact products themselves; the table is for callers and tests).
+#pragma clang fp contract(off)
+static std::vector<float> build_ftab(int interp)
+{
+    const int K = interp == V1C_INTER_LINEAR ? 2 : (interp == V1C_INTER_CUBIC ? 4 : 8);
+    std::vector<float> t1(32 * K);
+    for (int i = 0; i < 32; i++) {
+        if (K == 2) {
+            t1[i * 2 + 1] = i * (1.f / 32);
+            t1[i * 2] = 1.f - t1[i * 2 + 1];
+        } else {
+            coeffs_1d(interp, i * (1.f / 32), &t1[i * K]);
+        }
+    }
+    std::vector<float> tab((size_t)1024 * K * K);
+    for (int fy = 0; fy < 32; fy++)
+        for (int fx = 0; fx < 32; fx++)
+            for (int k1 = 0; k1 < K; k1++)
+                for (int k2 = 0; k2 < K; k2++)
+                    tab[((size_t)(fy * 32 + fx) * K + k1) * K + k2] = t1[fy * K + k1] * t1[fx * K + k2];
+    return tab;
+}
+#pragma clang fp contract(fast)
+
+extern "C" int v1c_build_ftab(int interp, float* out)
+{
+    if (!out || (interp != V1C_INTER_LINEAR && interp != V1C_INTER_CUBIC && interp != V1C_INTER_LANCZOS4))
+        return fail(V1C_E_INVALID, "v1c_build_ftab: interp must be LINEAR, CUBIC or LANCZOS4, out non-NULL");
+    const std::vector<float> tab = build_ftab(interp);
+    std::memcpy(out, tab.data(), tab.size() * sizeof(float));
+    return V1C_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// pixel types
+// ------------------------------------------------------------------------------------------
+static int depth_bytes(int depth)
+{
+    return depth == V1C_DEPTH_8U ? 1 : depth == V1C_DEPTH_16U ? 2 : depth == V1C_DEPTH_32F ? 4 : 0;
+}
+
+// cv2's saturate_cast of the border Scalar (doubles) to the pixel type: cvRound(double) is round half to even
+static void border_for_depth(int depth, const double* bv, uint8_t cval8[4], float cvalf[4])
+{
+    for (int k = 0; k < 4; k++) {
+        const double v = bv ? bv[k] : 0.0;
+        cval8[k] = (uint8_t)border_component(V1C_DEPTH_8U, v);  // (v1c_core.hpp)
+        cvalf[k] = border_component(depth, v);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // plan
 // ------------------------------------------------------------------------------------------
@@ -222,6 +275,8 @@ struct v1c_plan {
     hipEvent_t flags_ev = nullptr;
     hipStream_t flags_stream = nullptr;
     bool flags_pending = false;
+    int depth = V1C_DEPTH_8U;           // pixel type (V1C_DEPTH_*): wide depths run k_remap_wide only
+    WideArgs wide{};                    // ... with this border colour and weight table (device)
     std::atomic<int> last_launch{-1};   // V1C_LAUNCH_* of the most recent launch group of v1c_plan_run (tests: v1c_plan_last_launch)
     // v1c_plan_run_auto: a second device copy of the context whose Denormalize scale a small kernel rewrites from a device-resident radius
     // in front of every such launch; launches on different streams are ordered by an event, like the flag words
@@ -405,6 +460,15 @@ static MPolyTable cached_mpoly_table(const std::vector<v1c_op>& radial, const Ra
 extern "C" int v1c_plan_create(v1c_plan** out, int device, const v1c_chain* chain, int src_h, int src_w, int dst_h,
                                int dst_w, int cn, int interp, int border_mode, const uint8_t border_val[4])
 {
+    double bv[4] = {0, 0, 0, 0};
+    for (int k = 0; k < 4 && border_val; k++)
+        bv[k] = border_val[k];
+    return v1c_plan_create_ex(out, device, chain, src_h, src_w, dst_h, dst_w, cn, V1C_DEPTH_8U, interp, border_mode, bv);
+}
+
+extern "C" int v1c_plan_create_ex(v1c_plan** out, int device, const v1c_chain* chain, int src_h, int src_w, int dst_h,
+                                  int dst_w, int cn, int depth, int interp, int border_mode, const double border_val_f64[4])
+{
     if (!out)
         return fail(V1C_E_INVALID, "out is NULL");
     *out = nullptr;
@@ -414,6 +478,11 @@ extern "C" int v1c_plan_create(v1c_plan** out, int device, const v1c_chain* chai
     rc = validate_geom(src_h, src_w, dst_h, dst_w, cn, interp, border_mode);
     if (rc)
         return rc;
+    if (!depth_bytes(depth))
+        return fail(V1C_E_INVALID, "depth must be V1C_DEPTH_8U, V1C_DEPTH_16U or V1C_DEPTH_32F");
+    uint8_t border_val[4];
+    float cval_wide[4];
+    border_for_depth(depth, border_val_f64, border_val, cval_wide);
     DeviceGuard dg(device);
     if (!dg.ok)
         return fail(V1C_E_NODEVICE, "hipSetDevice failed");
@@ -434,6 +503,18 @@ extern "C" int v1c_plan_create(v1c_plan** out, int device, const v1c_chain* chai
     if (rc) {
         v1c_plan_destroy(p);
         return rc;
+    }
+    p->depth = depth;
+    if (depth != V1C_DEPTH_8U) {
+        for (int k = 0; k < 4; k++)
+            p->wide.cval[k] = cval_wide[k];
+        const int gi = p->ctx.g.interp;
+        if (gi == V1C_INTER_CUBIC || gi == V1C_INTER_LANCZOS4) {
+            if ((rc = upload(p, build_ftab(gi), &p->wide.ftab))) {
+                v1c_plan_destroy(p);
+                return rc;
+            }
+        }
     }
     for (int i = 0; i < chain->n_ops; i++)
         p->n_rot_stages += chain->ops[i].opcode == V1C_OP_ROTATE;
@@ -618,7 +699,8 @@ extern "C" int v1c_plan_create(v1c_plan** out, int device, const v1c_chain* chai
             t_up = now_ms();
             // source boxes of the tiled kernel, computed once (BGR, constant border, linear/cubic/lanczos4)
             const Geom& g = p->ctx.g;
-            if (cn_kernel_supports(g) && p->plan_shared_entry && !p->disable_shared_entry && p->gen_mode == 0) {
+            // (the tile kernels are uint8-only: a plan of a wide depth runs k_remap_wide and needs none of their boxes)
+            if (p->depth == V1C_DEPTH_8U && cn_kernel_supports(g) && p->plan_shared_entry && !p->disable_shared_entry && p->gen_mode == 0) {
                 // grayscale / BGRA: the same boxes, consumed by k_ray_lin_cn
                 void* bx = nullptr;
                 e = hipMalloc(&bx, tile_box_bytes(g));
@@ -640,7 +722,7 @@ extern "C" int v1c_plan_create(v1c_plan** out, int device, const v1c_chain* chai
                 if (const char* dbg = tuning_env("V1C_DEBUG"); dbg && dbg[0] == '1')
                     std::fprintf(stderr, "[v1c] cn = %d tile kernel: box buffers of %d KB\n", g.cn, p->cn_kb);
             }
-            if (tile_kernel_supports(g)) {
+            if (p->depth == V1C_DEPTH_8U && tile_kernel_supports(g)) {
                 void* bx = nullptr;
                 e = hipMalloc(&bx, tile_box_bytes(g));
                 if (e == hipSuccess) {
@@ -811,8 +893,11 @@ static int fill_unit(const v1c_plan* p, const v1c_unit& in, DevUnit& out)
     if (!in.src || !in.dst)
         return fail(V1C_E_INVALID, "unit src/dst is NULL");
     const Geom& g = p->ctx.g;
-    if (in.src_pitch < (int64_t)g.src_w * g.cn || in.dst_pitch < (int64_t)g.dst_w * g.cn)
+    const int eb = depth_bytes(p->depth);
+    if (in.src_pitch < (int64_t)g.src_w * g.cn * eb || in.dst_pitch < (int64_t)g.dst_w * g.cn * eb)
         return fail(V1C_E_INVALID, "unit pitch smaller than a row");
+    if (((uintptr_t)in.src | (uintptr_t)in.dst | (uint64_t)in.src_pitch | (uint64_t)in.dst_pitch) & (uint64_t)(eb - 1))
+        return fail(V1C_E_INVALID, "unit pointers and pitches must be multiples of the pixel size");
     if (in.has_rot && !p->chain_has_rot)
         return fail(V1C_E_INVALID, "unit carries a rotation but the plan's chain has no rotate stage");
     out.src = in.src, out.dst = in.dst;
@@ -947,6 +1032,47 @@ extern "C" int v1c_plan_release_captures(v1c_plan* p)
     return V1C_OK;
 }
 
+// Plans of a wide depth (16U / 32F): k_remap_wide with the generic kernels' mode decision -- the interpreter for literal plans and for
+// units that override one of several rotate stages (or the rotation of a general-mode plan), else the ray pass and, unless the plan
+// proves it unnecessary, the fix-up pass behind it (same tile-flag protocol and cross-stream ordering as the uint8 launches).  At most
+// kMaxUnitsPerLaunch units per launch: the flag words cover that many, and the units travel in the kernel arguments.
+static int run_wide(v1c_plan* p, hipStream_t st, const DevUnit* du, int n_units)
+{
+    for (int base = 0; base < n_units;) {
+        const int n = std::min(kMaxUnitsPerLaunch, n_units - base);
+        const DevUnit* u = du + base;
+        base += n;
+        const UnitArgs ua = unit_args(u, n);
+        int mode = MODE_LITERAL;
+        bool need_fixup = false;
+        if (p->mode == MODE_RAY) {
+            const LaunchPlan d = decide_launch(p, u, n);
+            if (!(d.any_rot && (p->n_rot_stages > 1 || p->gen_mode != 0)))
+                mode = MODE_RAY, need_fixup = d.need_fixup;
+        }
+        if (!need_fixup) {
+            HIP_TRY(launch_remap_wide(mode, p->depth, p->ctx, ua, p->wide, n, st));
+            p->last_launch.store(V1C_LAUNCH_WIDE, std::memory_order_relaxed);
+            continue;
+        }
+        std::lock_guard<std::mutex> flags_lk(p->flags_mu);
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cap) != hipSuccess)
+            cap = hipStreamCaptureStatusNone;
+        const bool capturing = cap != hipStreamCaptureStatusNone;
+        if (!capturing && p->flags_pending && p->flags_stream != st)
+            HIP_TRY(hipStreamWaitEvent(st, p->flags_ev, 0));
+        HIP_TRY(launch_remap_wide(MODE_RAY, p->depth, p->ctx, ua, p->wide, n, st));
+        HIP_TRY(launch_remap_wide(MODE_FIXUP, p->depth, p->ctx, ua, p->wide, n, st));
+        if (!capturing) {
+            HIP_TRY(hipEventRecord(p->flags_ev, st));
+            p->flags_stream = st, p->flags_pending = true;
+        }
+        p->last_launch.store(V1C_LAUNCH_WIDE | V1C_LAUNCH_FIXUP, std::memory_order_relaxed);
+    }
+    return V1C_OK;
+}
+
 extern "C" int v1c_plan_run(v1c_plan* p, void* stream, const v1c_unit* units, int n_units)
 {
     if (!p || !units || n_units <= 0)
@@ -967,6 +1093,8 @@ extern "C" int v1c_plan_run(v1c_plan* p, void* stream, const v1c_unit* units, in
         if (rc)
             return rc;
     }
+    if (p->depth != V1C_DEPTH_8U)
+        return run_wide(p, st, du, n_units);
     for (int base = 0; base < n_units;) {
         if (p->mode != MODE_RAY) {
             const int n = std::min(kMaxUnitsPerLaunch, n_units - base);
@@ -1083,6 +1211,8 @@ static int run_auto(v1c_plan* p, void* stream, const v1c_unit* units, int n_unit
         return fail(V1C_E_INVALID, "v1c_plan_run_auto: bad arguments");
     if (n_units > kInlineUnits)
         return fail(V1C_E_UNSUPPORTED, "v1c_plan_run_auto: at most 16 units per call");
+    if (p->depth != V1C_DEPTH_8U)
+        return fail(V1C_E_UNSUPPORTED, "v1c_plan_run_auto: 8-bit images only (16-bit / float32: take the radius to the host)");
     if (p->mode != MODE_RAY || p->gen_mode != 0 || p->ana.base != 0 || p->n_rot_stages > 1 || p->disable_fast)
         return fail(V1C_E_UNSUPPORTED, "v1c_plan_run_auto: chains of the form EquirectangularEncoder() * [one rotation] * radial stages only");
     // (the patch kernels write the scale (r, r): get_map's DenormalizeTransformer(scale=(radius, radius)), remapper.py:55 -- a plan made
@@ -1325,6 +1455,61 @@ extern "C" int v1c_remap_lut(int device, void* stream, const uint8_t* src, int s
     std::memset(&ua, 0, sizeof(ua));
     ua.u[0].src = src, ua.u[0].dst = dst, ua.u[0].src_pitch = src_pitch, ua.u[0].dst_pitch = dst_pitch;
     HIP_TRY(launch_remap(MODE_LUT, c, ua, 1, (hipStream_t)stream));
+    return V1C_OK;
+}
+
+extern "C" int v1c_remap_lut_ex(int device, void* stream, const void* src, int src_h, int src_w, int64_t src_pitch, int cn, int depth,
+                                void* dst, int dst_h, int dst_w, int64_t dst_pitch, const float* xmap, const float* ymap,
+                                int64_t map_pitch, int interp, int border_mode, const double border_val[4])
+{
+    const int eb = depth_bytes(depth);
+    if (!eb)
+        return fail(V1C_E_INVALID, "depth must be V1C_DEPTH_8U, V1C_DEPTH_16U or V1C_DEPTH_32F");
+    uint8_t cval8[4];
+    WideArgs wa{};
+    border_for_depth(depth, border_val, cval8, wa.cval);
+    if (depth == V1C_DEPTH_8U)
+        return v1c_remap_lut(device, stream, (const uint8_t*)src, src_h, src_w, src_pitch, cn, (uint8_t*)dst, dst_h, dst_w, dst_pitch, xmap,
+                             ymap, map_pitch, interp, border_mode, cval8);
+    int rc = validate_geom(src_h, src_w, dst_h, dst_w, cn, interp, border_mode);
+    if (rc)
+        return rc;
+    if (!src || !dst || !xmap || !ymap)
+        return fail(V1C_E_INVALID, "v1c_remap_lut_ex: NULL pointer");
+    if (map_pitch < (int64_t)dst_w * 4 || (map_pitch & 3))
+        return fail(V1C_E_INVALID, "map_pitch too small or not a multiple of 4");
+    if (src_pitch < (int64_t)src_w * cn * eb || dst_pitch < (int64_t)dst_w * cn * eb)
+        return fail(V1C_E_INVALID, "pitch smaller than a row");
+    if (((uintptr_t)src | (uintptr_t)dst | (uint64_t)src_pitch | (uint64_t)dst_pitch) & (uint64_t)(eb - 1))
+        return fail(V1C_E_INVALID, "pointers and pitches must be multiples of the pixel size");
+    DeviceGuard dg(device);
+    if (!dg.ok)
+        return fail(V1C_E_NODEVICE, "hipSetDevice failed");
+    // the float weight table: one per (device, interp), like v1c_remap_lut's int16 one
+    static std::mutex mu;
+    static std::map<std::pair<int, int>, const float*> ftabs;
+    KernelCtx c{};
+    Geom& g = c.g;
+    g.src_h = src_h, g.src_w = src_w, g.dst_h = dst_h, g.dst_w = dst_w, g.cn = cn;
+    g.interp = interp == V1C_INTER_AREA ? V1C_INTER_LINEAR : interp;
+    g.border = border_mode;
+    if (g.interp == V1C_INTER_CUBIC || g.interp == V1C_INTER_LANCZOS4) {
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = ftabs.find({device, g.interp});
+        if (it == ftabs.end()) {
+            const std::vector<float> tab = build_ftab(g.interp);
+            void* d = nullptr;
+            HIP_TRY(hipMalloc(&d, tab.size() * sizeof(float)));
+            HIP_TRY(hipMemcpy(d, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+            it = ftabs.emplace(std::make_pair(device, g.interp), (const float*)d).first;
+        }
+        wa.ftab = it->second;
+    }
+    c.xmap = xmap, c.ymap = ymap, c.map_pitch = map_pitch;
+    UnitArgs ua;
+    std::memset(&ua, 0, sizeof(ua));
+    ua.u[0].src = (const uint8_t*)src, ua.u[0].dst = (uint8_t*)dst, ua.u[0].src_pitch = src_pitch, ua.u[0].dst_pitch = dst_pitch;
+    HIP_TRY(launch_remap_wide(MODE_LUT, depth, c, ua, wa, 1, (hipStream_t)stream));
     return V1C_OK;
 }
 

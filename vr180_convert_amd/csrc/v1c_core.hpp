@@ -662,4 +662,203 @@ V1C_HDF bool sample(const Image& s, const Geom& g, const short* itab, float x, f
     return sample_table<CN, 8>(s, g, itab, x, y, out);
 }
 
+// ------------------------------------------------------------------------------------------
+// sampler of 16-bit unsigned (CV_16U) and float32 (CV_32F) images: remapNearest / remapBilinear / remapBicubic / remapLanczos4
+// instantiated with float weights ("16-bit and float32 images"; unpinned: restated, not measured against cv2).
+// The same coordinates (quantize: 1/32 buckets), taps and border decisions as the uint8 sampler above, but float32 arithmetic:
+//   * weights wf[fy*32+fx][k1][k2] = t1d[fy][k1] * t1d[fx][k2] (build_ftab, plan.hip) -- for LINEAR t1d = {1 - k/32, k/32}, whose
+//     products are exact and are formed here instead of read;
+//   * every product and sum rounded on its own, left to right (no contraction: the pragma below);
+//   * footprints that are not wholly inside start from the border colour: cv + sum over the valid taps of (p - cv) * w -- exact in
+//     integers, where the uint8 sampler substitutes cv per tap instead, but not in float;
+//   * result: 16U cvRound (half to even) saturated to [0, 65535], NaN -> 0; 32F as summed.
+// `Image::p` / `pitch` are in bytes; `cval` = the border colour already saturated to T, held as float (exact for 16U).
+// ------------------------------------------------------------------------------------------
+#pragma clang fp contract(off)
+
+// cv2's saturate_cast of one component of the border Scalar (a double) to the pixel type of `depth` (V1C_DEPTH_*), held as the float the
+// samplers read: 8U / 16U cvRound(double) -- half to even; NaN and |v| >= 2^31 give INT_MIN -- clamped to [0, 255] / [0, 65535], 32F
+// (float)v.  (Host: v1c_plan_create_ex / v1c_remap_lut_ex; the test harness of tests/host_wide calls it too.)
+V1C_HD float border_component(int depth, double v)
+{
+    const double r = fabs(v) < 2147483648.0 ? nearbyint(v) : -2147483648.0;
+    if (depth == V1C_DEPTH_8U)
+        return (float)(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));
+    if (depth == V1C_DEPTH_16U)
+        return (float)(r < 0.0 ? 0.0 : (r > 65535.0 ? 65535.0 : r));
+    return (float)v;
+}
+
+template <typename T>
+V1C_HDF T wide_cast(float v);
+
+template <>
+V1C_HDF uint16_t wide_cast<uint16_t>(float v)
+{
+    const int r = cv_round(v);  // NaN / out of range: INT_MIN -> 0
+    return (uint16_t)(r < 0 ? 0 : (r > 65535 ? 65535 : r));
+}
+
+template <>
+V1C_HDF float wide_cast<float>(float v)
+{
+    return v;
+}
+
+template <typename T>
+V1C_HDF const T* wide_row(const Image& s, int y)
+{
+    return (const T*)(s.p + (int64_t)y * s.pitch);
+}
+
+template <typename T, int CN>
+V1C_HD bool wide_nearest(const Image& s, const Geom& g, const float* cval, float x, float y, T* out)
+{
+    int sx = clamp_short(cv_round(x)), sy = clamp_short(cv_round(y));
+    if (!((unsigned)sx < (unsigned)s.w && (unsigned)sy < (unsigned)s.h)) {
+        if (g.border == V1C_BORDER_TRANSPARENT)
+            return false;
+        if (g.border == V1C_BORDER_CONSTANT) {
+#pragma unroll
+            for (int k = 0; k < CN; k++)
+                out[k] = (T)cval[k];
+            return true;
+        }
+        sx = border_index(sx, s.w, g.border);
+        sy = border_index(sy, s.h, g.border);
+    }
+    const T* S = wide_row<T>(s, sy) + (int64_t)sx * CN;
+#pragma unroll
+    for (int k = 0; k < CN; k++)
+        out[k] = S[k];
+    return true;
+}
+
+template <typename T, int CN>
+V1C_HD bool wide_linear(const Image& s, const Geom& g, const float* cval, float x, float y, T* out)
+{
+    const Taps t = quantize(x, y);
+    const float tx1 = (float)t.fx * 0.03125f, ty1 = (float)t.fy * 0.03125f;
+    const float tx0 = 1.0f - tx1, ty0 = 1.0f - ty1;
+    const float w0 = ty0 * tx0, w1 = ty0 * tx1, w2 = ty1 * tx0, w3 = ty1 * tx1;  // = build_ftab(LINEAR), exactly
+    const int W = s.w, H = s.h;
+    int x0, x1, y0, y1;
+    if ((unsigned)t.ix < (unsigned)(W - 1) && (unsigned)t.iy < (unsigned)(H - 1)) {
+        x0 = t.ix, x1 = t.ix + 1, y0 = t.iy, y1 = t.iy + 1;
+    } else {
+        if (g.border == V1C_BORDER_CONSTANT && (t.ix >= W || t.ix + 1 < 0 || t.iy >= H || t.iy + 1 < 0)) {
+#pragma unroll
+            for (int k = 0; k < CN; k++)
+                out[k] = (T)cval[k];
+            return true;
+        }
+        if (g.border == V1C_BORDER_TRANSPARENT)
+            return false;
+        x0 = border_index(t.ix, W, g.border);
+        x1 = border_index(t.ix + 1, W, g.border);
+        y0 = border_index(t.iy, H, g.border);
+        y1 = border_index(t.iy + 1, H, g.border);
+    }
+    const T* r0 = wide_row<T>(s, y0 < 0 ? 0 : y0);
+    const T* r1 = wide_row<T>(s, y1 < 0 ? 0 : y1);
+#pragma unroll
+    for (int k = 0; k < CN; k++) {
+        const float cv = cval[k];
+        const float p00 = (x0 >= 0 && y0 >= 0) ? (float)r0[x0 * CN + k] : cv;
+        const float p01 = (x1 >= 0 && y0 >= 0) ? (float)r0[x1 * CN + k] : cv;
+        const float p10 = (x0 >= 0 && y1 >= 0) ? (float)r1[x0 * CN + k] : cv;
+        const float p11 = (x1 >= 0 && y1 >= 0) ? (float)r1[x1 * CN + k] : cv;
+        out[k] = wide_cast<T>(((p00 * w0 + p01 * w1) + p10 * w2) + p11 * w3);
+    }
+    return true;
+}
+
+// CUBIC (K = 4, origin (ix - 1, iy - 1)) / LANCZOS4 (K = 8, origin (ix - 3, iy - 3)); `ftab` laid out [fy*32+fx][K][K]
+template <typename T, int CN, int K>
+V1C_HD bool wide_table(const Image& s, const Geom& g, const float* cval, const float* __restrict__ ftab, float x, float y, T* out)
+{
+    const Taps t = quantize(x, y);
+    const float* __restrict__ w = ftab + (size_t)(t.fy * 32 + t.fx) * (K * K);
+    const int off = K / 2 - 1;
+    const int sx = t.ix - off, sy = t.iy - off;
+    const int W = s.w, H = s.h;
+    float sum[CN];
+    if ((unsigned)sx < (unsigned)(W - (K - 1) > 0 ? W - (K - 1) : 0) && (unsigned)sy < (unsigned)(H - (K - 1) > 0 ? H - (K - 1) : 0)) {
+        // each row one left-to-right sum; CUBIC starts from row 0's, LANCZOS4 from 0
+#pragma unroll
+        for (int k = 0; k < CN; k++)
+            sum[k] = 0.0f;
+        for (int i = 0; i < K; i++) {
+            const T* S = wide_row<T>(s, sy + i) + (int64_t)sx * CN;
+            float r[CN];
+#pragma unroll
+            for (int k = 0; k < CN; k++)
+                r[k] = (float)S[k] * w[i * K];
+#pragma unroll
+            for (int j = 1; j < K; j++) {
+                const float wv = w[i * K + j];
+#pragma unroll
+                for (int k = 0; k < CN; k++)
+                    r[k] = r[k] + (float)S[j * CN + k] * wv;
+            }
+#pragma unroll
+            for (int k = 0; k < CN; k++)
+                sum[k] = (K == 4 && i == 0) ? r[k] : sum[k] + r[k];
+        }
+    } else {
+        int border = g.border;
+        if (border == V1C_BORDER_TRANSPARENT) {
+            if ((unsigned)(sx + off) >= (unsigned)W || (unsigned)(sy + off) >= (unsigned)H)
+                return false;
+            border = V1C_BORDER_REFLECT_101;
+        }
+        if (border == V1C_BORDER_CONSTANT && (sx >= W || sx + K <= 0 || sy >= H || sy + K <= 0)) {
+#pragma unroll
+            for (int k = 0; k < CN; k++)
+                out[k] = (T)cval[k];
+            return true;
+        }
+        int xs[K];
+#pragma unroll
+        for (int j = 0; j < K; j++)
+            xs[j] = border_index(sx + j, W, border);
+#pragma unroll
+        for (int k = 0; k < CN; k++)
+            sum[k] = cval[k];
+        for (int i = 0; i < K; i++) {
+            const int yi = border_index(sy + i, H, border);
+            if (yi < 0)
+                continue;
+            const T* S = wide_row<T>(s, yi);
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                if (xs[j] < 0)
+                    continue;
+                const float wv = w[i * K + j];
+#pragma unroll
+                for (int k = 0; k < CN; k++)
+                    sum[k] = sum[k] + ((float)S[xs[j] * CN + k] - cval[k]) * wv;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < CN; k++)
+        out[k] = wide_cast<T>(sum[k]);
+    return true;
+}
+
+template <typename T, int CN, int INTERP>
+V1C_HDF bool sample_wide(const Image& s, const Geom& g, const float* cval, const float* ftab, float x, float y, T* out)
+{
+    if (INTERP == V1C_INTER_NEAREST)
+        return wide_nearest<T, CN>(s, g, cval, x, y, out);
+    if (INTERP == V1C_INTER_LINEAR)
+        return wide_linear<T, CN>(s, g, cval, x, y, out);
+    if (INTERP == V1C_INTER_CUBIC)
+        return wide_table<T, CN, 4>(s, g, cval, ftab, x, y, out);
+    return wide_table<T, CN, 8>(s, g, cval, ftab, x, y, out);
+}
+
+#pragma clang fp contract(fast)
+
 }  // namespace v1c

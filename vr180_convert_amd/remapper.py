@@ -73,9 +73,29 @@ def border_scalar(value: Any) -> np.ndarray:
     return out
 
 
+def border_scalar_f64(value: Any) -> np.ndarray:
+    """Python ``borderValue`` -> the float64[4] cv2 Scalar itself (a bare number sets only component 0, a tuple the leading
+    components): what ``v1c_plan_create_ex`` saturates to the pixel type of a 16-bit or float32 image."""
+    vals = [value] if np.isscalar(value) else list(value)
+    out = np.zeros(4, np.float64)
+    for i, v in enumerate(vals[:4]):
+        out[i] = float(v)
+    return out
+
+
+# pixel types cv2.remap takes (CV_8U, CV_16U, CV_32F) -> the engine's depth codes; anything else raises TypeError
+DEPTHS = {torch.uint8: _abi.DEPTH_8U, torch.uint16: _abi.DEPTH_16U, torch.float32: _abi.DEPTH_32F}
+NP_DTYPES = (np.uint8, np.uint16, np.float32)
+
+
+def _border_key(value: Any, dtype: torch.dtype) -> bytes:
+    """The part of a cache key the border colour decides: the saturated uint8 colour for 8-bit images (as ever), the Scalar otherwise."""
+    return border_scalar(value).tobytes() if dtype == torch.uint8 else border_scalar_f64(value).tobytes()
+
+
 def _check_image_tensor(t: torch.Tensor, what: str) -> None:
-    if t.dtype != torch.uint8 or t.dim() != 3:
-        raise TypeError(f"{what} must be a uint8 (H, W, C) tensor")
+    if t.dtype not in DEPTHS or t.dim() != 3:
+        raise TypeError(f"{what} must be a uint8, uint16 or float32 (H, W, C) tensor")
     cn = t.shape[2]
     if (cn > 1 and t.stride(2) != 1) or (t.shape[1] > 1 and t.stride(1) != cn) or (
         t.shape[0] > 1 and t.stride(0) < t.shape[1] * cn
@@ -84,22 +104,26 @@ def _check_image_tensor(t: torch.Tensor, what: str) -> None:
 
 
 def marshal_units(srcs: Sequence[torch.Tensor], dsts: Sequence[torch.Tensor], rots: Sequence[Any] | None, *,
-                  src_hw: tuple[int, int], dst_wh: tuple[int, int], cn: int, device: torch.device | None):
+                  src_hw: tuple[int, int], dst_wh: tuple[int, int], cn: int, device: torch.device | None,
+                  dtype: torch.dtype | None = None):
     """The ``v1c_unit`` array of a launch (include/vr180_remap.h): one record per eye -- pointers and row
     pitches of its source view and of ITS half of the side-by-side output (remapper.py:517-518 becomes a
-    pitch), optionally the 3x3 rotation replacing the chain's.  Validates shapes, layout and device;
+    pitch, in bytes), optionally the 3x3 rotation replacing the chain's.  Validates shapes, layout, pixel type and device;
     ``device=None`` skips the device check (the multi-rank CPU tests marshal host tensors)."""
     n = len(srcs)
     units = (_abi.Unit * n)()
     for k, (s, d) in enumerate(zip(srcs, dsts)):
         _check_image_tensor(s, "src")
         _check_image_tensor(d, "dst")
+        if s.dtype != d.dtype or (dtype is not None and s.dtype != dtype):
+            raise TypeError(f"unit {k}: src {s.dtype} / dst {d.dtype}: source and destination must both have the plan's pixel type"
+                            + ("" if dtype is None else f" ({dtype})"))
         if tuple(s.shape) != (*src_hw, cn) or tuple(d.shape) != (dst_wh[1], dst_wh[0], cn):
             raise ValueError(f"unit {k}: tensor shapes {tuple(s.shape)} -> {tuple(d.shape)} do not match the plan")
         if device is not None and (s.device != device or d.device != device):
             raise ValueError(f"unit {k}: tensors must live on {device}")
         units[k].src, units[k].dst = s.data_ptr(), d.data_ptr()
-        units[k].src_pitch, units[k].dst_pitch = s.stride(0), d.stride(0)
+        units[k].src_pitch, units[k].dst_pitch = s.stride(0) * s.element_size(), d.stride(0) * d.element_size()
         if rots is not None and rots[k] is not None:
             m = np.asarray(rots[k], dtype=np.float64).reshape(9)
             units[k].has_rot = 1
@@ -111,18 +135,30 @@ def marshal_units(srcs: Sequence[torch.Tensor], dsts: Sequence[torch.Tensor], ro
 class Plan:
     """Owner of one ``v1c_plan`` (see include/vr180_remap.h: v1c_plan_create)."""
 
-    def __init__(self, chain: _abi.Chain, *, src_hw, dst_wh, cn, interpolation, border_mode, border_value, device):
+    def __init__(self, chain: _abi.Chain, *, src_hw, dst_wh, cn, interpolation, border_mode, border_value, device,
+                 dtype: torch.dtype = torch.uint8):
         self.device = _device(device)
         self.src_hw, self.dst_wh, self.cn = tuple(src_hw), tuple(dst_wh), int(cn)
+        if dtype not in DEPTHS:
+            raise TypeError(f"pixel type {dtype}: uint8, uint16 or float32 only (cv2.remap's CV_8U / CV_16U / CV_32F)")
+        self.dtype = dtype
         self._h = C.c_void_p()
         self._memo: "OrderedDict[tuple, Any]" = OrderedDict()  # marshalled unit arrays of recent buffer sets
-        bv = border_scalar(border_value)
         t0 = time.perf_counter()
-        rc = _native.lib().v1c_plan_create(
-            C.byref(self._h), self.device.index, C.byref(chain), src_hw[0], src_hw[1], dst_wh[1], dst_wh[0],
-            cn, int(interpolation), int(border_mode), bv.ctypes.data,
-        )
-        _native.check(rc, "v1c_plan_create")
+        if dtype == torch.uint8:
+            bv = border_scalar(border_value)
+            rc = _native.lib().v1c_plan_create(
+                C.byref(self._h), self.device.index, C.byref(chain), src_hw[0], src_hw[1], dst_wh[1], dst_wh[0],
+                cn, int(interpolation), int(border_mode), bv.ctypes.data,
+            )
+            _native.check(rc, "v1c_plan_create")
+        else:  # 16-bit / float32 (k_remap_wide): the border colour travels as cv2's Scalar of doubles
+            bv = border_scalar_f64(border_value)
+            rc = _native.lib().v1c_plan_create_ex(
+                C.byref(self._h), self.device.index, C.byref(chain), src_hw[0], src_hw[1], dst_wh[1], dst_wh[0],
+                cn, DEPTHS[dtype], int(interpolation), int(border_mode), bv.ctypes.data,
+            )
+            _native.check(rc, "v1c_plan_create_ex")
         self.create_ms = (time.perf_counter() - t0) * 1e3  # synchronous: host analysis + table uploads + tile boxes
 
     @property
@@ -133,7 +169,8 @@ class Plan:
 
     def last_launch(self) -> str:
         """Kernel family of this plan's most recent launch group (``v1c_plan_last_launch``): 'generic', 'tile', 'mirror', 'batch',
-        'rot_pair', 'cn' or 'cn_rot', with '+fixup' when a fix-up pass followed; '' before the first run.  For tests and the bench."""
+        'rot_pair', 'cn', 'cn_rot' or 'wide' (16-bit / float32 images), with '+fixup' when a fix-up pass followed; '' before the first
+        run.  For tests and the bench."""
         k = _native.lib().v1c_plan_last_launch(self._h)
         if k < 0:
             return ""
@@ -158,7 +195,7 @@ class Plan:
                 rc = _native.lib().v1c_plan_run(self._h, _stream_ptr(self.device), units, n)
                 _native.check(rc, "v1c_plan_run")
                 return
-        units = marshal_units(srcs, dsts, rots, src_hw=self.src_hw, dst_wh=self.dst_wh, cn=self.cn, device=self.device)
+        units = marshal_units(srcs, dsts, rots, src_hw=self.src_hw, dst_wh=self.dst_wh, cn=self.cn, device=self.device, dtype=self.dtype)
         rc = _native.lib().v1c_plan_run(self._h, _stream_ptr(self.device), units, n)
         _native.check(rc, "v1c_plan_run")
         if sig is not None:
@@ -174,8 +211,8 @@ class Plan:
         """``v1c_plan_run_auto``: the launch with the radius read from device memory -- ``rad`` = float64 ``(n, 2)`` (radius, status)
         pairs as ``v1c_get_radius_async`` writes them; the launch uses their maximum.  ``rad=None``: the estimates are taken from
         ``srcs`` themselves by the same call (``v1c_plan_run_auto_images``, ``threshold`` = get_radius's).  Raises NotImplementedError
-        for chains / geometries the device-resident form does not serve (the caller then takes the radius to the host)."""
-        units = marshal_units(srcs, dsts, rots, src_hw=self.src_hw, dst_wh=self.dst_wh, cn=self.cn, device=self.device)
+        for chains / geometries / pixel types the device-resident form does not serve (the caller then takes the radius to the host)."""
+        units = marshal_units(srcs, dsts, rots, src_hw=self.src_hw, dst_wh=self.dst_wh, cn=self.cn, device=self.device, dtype=self.dtype)
         if rad is None:
             rc = _native.lib().v1c_plan_run_auto_images(self._h, _stream_ptr(self.device), units, len(srcs), int(threshold))
             _native.check(rc, "v1c_plan_run_auto_images")
@@ -257,10 +294,11 @@ def clear_caches() -> None:
         _AUTO_LAST.clear()
 
 
-def _plan_for(chain: _abi.Chain, *, src_hw, dst_wh, cn, interpolation, border_mode, border_value, device) -> Plan:
+def _plan_for(chain: _abi.Chain, *, src_hw, dst_wh, cn, interpolation, border_mode, border_value, device,
+              dtype: torch.dtype = torch.uint8) -> Plan:
     dev = _device(device)
     key = (chain.key(), tuple(src_hw), tuple(dst_wh), cn, int(interpolation), int(border_mode),
-           border_scalar(border_value).tobytes(), dev.index)
+           _border_key(border_value, dtype), dev.index, dtype)
     with _PLANS_LOCK:
         plan = _PLANS.get(key)
         if plan is not None:
@@ -268,7 +306,7 @@ def _plan_for(chain: _abi.Chain, *, src_hw, dst_wh, cn, interpolation, border_mo
             return plan
     # created outside the lock (tens of ms: other devices' threads keep going); a racing duplicate is dropped
     plan = Plan(chain, src_hw=src_hw, dst_wh=dst_wh, cn=cn, interpolation=interpolation,
-                border_mode=border_mode, border_value=border_value, device=dev)
+                border_mode=border_mode, border_value=border_value, device=dev, dtype=dtype)
     with _PLANS_LOCK:
         plan = _PLANS.setdefault(key, plan)
         _PLANS.move_to_end(key)
@@ -415,14 +453,17 @@ def remap_tensors(
         return _remap_with_rotations(transformer, srcs, dsts, rotations, radius=radius, interpolation=interpolation,
                                      boarder_mode=boarder_mode, boarder_value=boarder_value, size_input=size_input)
     # one shared transformer, same geometry and parameters as the previous call: straight to its plan
-    # (the key is the chain's exact parameter set, see _param_key)
+    # (the key is the chain's exact parameter set, see _param_key, and the shape and pixel type of EVERY unit: a call whose units
+    #  differ in either -- the halves of an odd-width frame, images of several types -- needs one plan per kind and never matches
+    #  the memo of a call with one kind)
     memo_key = None
     if not isinstance(transformer, (list, tuple)) and len(dsts) == n and isinstance(srcs[0], torch.Tensor) and isinstance(dsts[0], torch.Tensor):
         tk = _transformer_key(transformer)
         if tk is not None and srcs[0].dim() == 3 and dsts[0].dim() == 3:
             try:
-                memo_key = (tk, float(radius).hex(), srcs[0].shape, dsts[0].shape, int(interpolation), int(boarder_mode),
-                            border_scalar(boarder_value).tobytes(), None if size_input is None else tuple(size_input), srcs[0].device)
+                units_key = tuple([(s.shape, s.dtype) for s in srcs] + [(d.shape, d.dtype) for d in dsts])
+                memo_key = (tk, float(radius).hex(), units_key, int(interpolation), int(boarder_mode),
+                            _border_key(boarder_value, srcs[0].dtype), None if size_input is None else tuple(size_input), srcs[0].device)
             except (TypeError, ValueError):
                 memo_key = None
             last = _LAST_SHARED[0]  # (one read: another thread may replace the entry at any time)
@@ -432,6 +473,9 @@ def remap_tensors(
                 _TLS.plans = [plan]
                 return [plan.path_cached]
     dev = srcs[0].device
+    for k, (s_, d_) in enumerate(zip(srcs, dsts)):
+        if s_.dtype != d_.dtype:
+            raise TypeError(f"unit {k}: src {s_.dtype} / dst {d_.dtype}: source and destination must have one pixel type")
     cn = int(srcs[0].shape[2])
     dst_wh = (int(dsts[0].shape[1]), int(dsts[0].shape[0]))
     groups, host_mapped = group_units(transformer, srcs, dsts, radius=radius, size_input=size_input)
@@ -440,19 +484,31 @@ def remap_tensors(
     for k, t, size_in_k in host_mapped:
         xm, ym = _host_map(t, radius=radius, size_input=size_in_k, size_output=dst_wh)
         xm_d, ym_d = torch.from_numpy(xm).to(dev), torch.from_numpy(ym).to(dev)
-        bv = border_scalar(boarder_value)
         _check_image_tensor(srcs[k], "src")
         _check_image_tensor(dsts[k], "dst")
-        rc = _native.lib().v1c_remap_lut(
-            dev.index, _stream_ptr(dev), srcs[k].data_ptr(), srcs[k].shape[0], srcs[k].shape[1], srcs[k].stride(0), cn,
-            dsts[k].data_ptr(), dst_wh[1], dst_wh[0], dsts[k].stride(0), xm_d.data_ptr(), ym_d.data_ptr(),
-            xm_d.stride(0) * 4, int(interpolation), int(boarder_mode), bv.ctypes.data,
-        )
-        _native.check(rc, "v1c_remap_lut")
+        if srcs[k].dtype != dsts[k].dtype:
+            raise TypeError(f"unit {k}: src {srcs[k].dtype} / dst {dsts[k].dtype}: source and destination must have one pixel type")
+        if srcs[k].dtype == torch.uint8:
+            bv = border_scalar(boarder_value)
+            rc = _native.lib().v1c_remap_lut(
+                dev.index, _stream_ptr(dev), srcs[k].data_ptr(), srcs[k].shape[0], srcs[k].shape[1], srcs[k].stride(0), cn,
+                dsts[k].data_ptr(), dst_wh[1], dst_wh[0], dsts[k].stride(0), xm_d.data_ptr(), ym_d.data_ptr(),
+                xm_d.stride(0) * 4, int(interpolation), int(boarder_mode), bv.ctypes.data,
+            )
+            _native.check(rc, "v1c_remap_lut")
+        else:
+            bv = border_scalar_f64(boarder_value)
+            es = srcs[k].element_size()
+            rc = _native.lib().v1c_remap_lut_ex(
+                dev.index, _stream_ptr(dev), srcs[k].data_ptr(), srcs[k].shape[0], srcs[k].shape[1], srcs[k].stride(0) * es, cn,
+                DEPTHS[srcs[k].dtype], dsts[k].data_ptr(), dst_wh[1], dst_wh[0], dsts[k].stride(0) * es, xm_d.data_ptr(),
+                ym_d.data_ptr(), xm_d.stride(0) * 4, int(interpolation), int(boarder_mode), bv.ctypes.data,
+            )
+            _native.check(rc, "v1c_remap_lut_ex")
         paths.append("lut")
     for g in groups:
         plan = _plan_for(g.chain, src_hw=g.src_hw, dst_wh=dst_wh, cn=cn, interpolation=interpolation,
-                         border_mode=boarder_mode, border_value=boarder_value, device=dev)
+                         border_mode=boarder_mode, border_value=boarder_value, device=dev, dtype=g.srcs[0].dtype)
         plan.run(g.srcs, g.dsts, g.rots)
         _TLS.plans.append(plan)
         paths.append(plan.path)
@@ -476,7 +532,7 @@ class LaunchGroup:
 def group_units(transformer, srcs, dsts, *, radius: float, size_input: tuple[int, int] | None = None):
     """Host logic of a call, no device involved: lower the chain of every unit (one shared transformer or
     one per unit), split units into groups that share a plan -- same chain up to the matrix of a single
-    rotate stage, same source size -- and list the units whose chain cannot be lowered.
+    rotate stage, same source size, same pixel type -- and list the units whose chain cannot be lowered.
 
     Returns ``(groups, host_mapped)``: ``LaunchGroup`` records in first-appearance order and
     ``(unit index, transformer, size_input)`` for units that take the map from their own ``transform()``.
@@ -509,7 +565,8 @@ def group_units(transformer, srcs, dsts, *, radius: float, size_input: tuple[int
             host_mapped.append((k, t, size_in_k))
             continue
         shared, rot = _split_single_rotation(chain)
-        key = bytes(shared) + repr(tuple(srcs[k].shape)).encode()  # different source sizes: different plans
+        # different source sizes or pixel types: different plans
+        key = bytes(shared) + repr(tuple(srcs[k].shape)).encode() + str(getattr(srcs[k], "dtype", "")).encode()
         g = acc.setdefault(key, {"chain": shared, "full": chain, "src_hw": tuple(int(v) for v in srcs[k].shape[:2]),
                                  "srcs": [], "dsts": [], "rots": [], "index": []})
         g["srcs"].append(srcs[k])
@@ -541,7 +598,7 @@ def _remap_with_rotations(transformer, srcs, dsts, rotations, *, radius, interpo
     if rot is None:
         raise ValueError("rotations= needs a chain with exactly one Euclidean3DRotator")
     plan = _plan_for(shared, src_hw=src_hw, dst_wh=dst_wh, cn=int(srcs[0].shape[2]), interpolation=interpolation,
-                     border_mode=boarder_mode, border_value=boarder_value, device=dev)
+                     border_mode=boarder_mode, border_value=boarder_value, device=dev, dtype=srcs[0].dtype)
     plan.run(srcs, dsts, [as_rotation_matrix(r) for r in rotations])
     _TLS.plans = [plan]
     return [plan.path]
@@ -585,6 +642,13 @@ def get_radius_smart(radius: float | Literal["auto", "max"], images: Sequence[An
 
 
 def _get_radius_any(im: Any, threshold: int = 10) -> float:
+    if isinstance(im, torch.Tensor) and im.is_cuda and im.dtype != torch.uint8:
+        # 16-bit / float32 on the device: the scan kernel is 8-bit; the centre row (landscape) or column (transformer.py:126-129) is all
+        # the estimate reads -- it alone comes to the host, as a (1, W, C) / (H, 1, C) image with the same centre line
+        _check_image_tensor(im, "image")
+        h, w = int(im.shape[0]), int(im.shape[1])
+        line = im[h // 2][None] if w > h else im[:, w // 2][:, None]
+        return float(get_radius(line.cpu().numpy(), threshold=threshold))
     if isinstance(im, torch.Tensor) and im.is_cuda:
         _check_image_tensor(im, "image")
         r = C.c_double()
@@ -601,8 +665,8 @@ def _to_device(img: Any, dev: torch.device) -> torch.Tensor:
     if isinstance(img, torch.Tensor):
         return img if img.device == dev else img.to(dev)
     a = np.asarray(img)
-    if a.dtype != np.uint8:
-        raise TypeError("images must be uint8")  # cv2.remap's fixed-point path is the uint8 one
+    if a.dtype not in NP_DTYPES:
+        raise TypeError(f"images must be uint8, uint16 or float32, not {a.dtype}")  # cv2.remap's CV_8U / CV_16U / CV_32F
     if a.ndim == 2:
         a = a[..., None]
     # column-sliced views (remapper.py:455-456) are made contiguous on the host before upload; read-only arrays
@@ -625,9 +689,10 @@ def apply(
 ) -> Sequence[NDArray[np.uint8]]:
     """Apply transformer to images (reference remapper.py:324-403).
 
-    Returns one ``(size_output[1], size_output[0], C)`` uint8 array per input (CUDA tensors in ->
-    CUDA tensors out).  One map is shared by all images and, like the reference, takes its
-    geometry from ``images[0]``."""
+    Returns one ``(size_output[1], size_output[0], C)`` array per input, of the input's pixel type
+    (uint8, uint16 or float32; CUDA tensors in -> CUDA tensors out).  One map is shared by all
+    images and, like the reference, takes its geometry from ``images[0]``; images of different
+    pixel types are remapped by one plan per type."""
     in_paths_ = [in_paths] if isinstance(in_paths, (str, Path, np.ndarray, torch.Tensor)) else in_paths
     out_paths_ = [out_paths] if isinstance(out_paths, (str, Path)) else out_paths
     del in_paths, out_paths
@@ -657,7 +722,7 @@ def apply(
 
     srcs = [_to_device(im, dev) for im in images]
     cn = srcs[0].shape[2]
-    dsts = [torch.empty((size_output[1], size_output[0], cn), dtype=torch.uint8, device=dev) for _ in srcs]
+    dsts = [torch.empty((size_output[1], size_output[0], cn), dtype=s.dtype, device=dev) for s in srcs]
     if boarder_mode == _abi.BORDER_TRANSPARENT:
         for d in dsts:  # cv2 leaves skipped pixels uninitialised; make them deterministic
             d.zero_()
@@ -681,6 +746,8 @@ def auto_radius_tensor(images: Sequence[torch.Tensor], threshold: int = 10) -> t
     rad = torch.empty((len(images), 2), dtype=torch.float64, device=dev)
     for k, im in enumerate(images):
         _check_image_tensor(im, "image")
+        if im.dtype != torch.uint8:  # (the scan kernel reads bytes; 16-bit / float32: _get_radius_any, on the host)
+            raise TypeError(f"auto_radius_tensor: uint8 images only, not {im.dtype}")
         rc = _native.lib().v1c_get_radius_async(dev.index, _stream_ptr(dev), im.data_ptr(), im.shape[0], im.shape[1], im.stride(0), im.shape[2],
                                                 threshold, rad.data_ptr() + 16 * k)
         _native.check(rc, "v1c_get_radius_async")
@@ -704,6 +771,9 @@ def remap_tensors_auto(transformer: TransformerBase, srcs: Sequence[torch.Tensor
     bytes the caller's fallback writes again)."""
     if isinstance(transformer, (list, tuple)):
         raise ValueError("remap_tensors_auto takes ONE transformer (per-eye transformers: one call per eye, as apply_lr does)")
+    if any(s.dtype != torch.uint8 for s in srcs):
+        # (the device-resident radius is 8-bit only: 16-bit / float32 images take the exact form, the estimate on the host)
+        raise NotImplementedError("remap_tensors_auto: 8-bit images only (16-bit / float32: the radius goes to the host)")
     dev = srcs[0].device
     src_hw = (int(srcs[0].shape[0]), int(srcs[0].shape[1]))
     dst_wh = (int(dsts[0].shape[1]), int(dsts[0].shape[0]))
@@ -743,7 +813,7 @@ def _remap_host_radius(transformer: TransformerBase, srcs, dsts, r: float, *, in
     circle that repeats (the same estimate twice in a row) gets its own plan and the planned kernels.  Same bytes either way.
     False: not served (chains the device-resident launch does not take, a repeated radius) -- the caller runs the planned path."""
     k = _transformer_key(transformer)
-    if k is None:
+    if k is None or any(s.dtype != torch.uint8 for s in srcs):
         return False
     dev = srcs[0].device
     key = (k, tuple(size_input), tuple(int(v) for v in dsts[0].shape[:2]), int(srcs[0].shape[2]), int(interpolation), int(boarder_mode),
@@ -785,11 +855,15 @@ def apply_lr_tensors(
     synchronisation; raises IndexError like the reference when an image has no black border; a circle that moved is served by the
     launch that reads the radius from device memory -- no plan per radius --, a circle that repeats by a plan of its own).
     ``auto_radius_on_device=True`` keeps it on the device (``remap_tensors_auto``): no synchronisation, one plan for every radius,
-    graph-capturable; default (None): taken when the current stream is being captured into a graph, where a synchronisation is illegal."""
+    graph-capturable; default (None): taken when the current stream is being captured into a graph, where a synchronisation is illegal.
+
+    uint16 / float32 eyes give an output of their type.  Their radius="auto" always takes the exact form (the device-resident one is
+    8-bit only): under graph capture with ``auto_radius_on_device=None`` the NotImplementedError of ``remap_tensors_auto`` propagates,
+    as it does for chains that form does not serve -- pass a numeric radius there."""
     w, h = size_output
     cn = left.shape[2]
     if out is None:
-        out = torch.empty((h, 2 * w, cn), dtype=torch.uint8, device=left.device)
+        out = torch.empty((h, 2 * w, cn), dtype=left.dtype, device=left.device)
         if boarder_mode == _abi.BORDER_TRANSPARENT:
             out.zero_()
     halves = [out[:, :w], out[:, w:]]
@@ -839,6 +913,8 @@ def anaglyph_tensors(left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
     ``combine`` (the "L" / "R" labels of :498-516 are not drawn here).  Current stream, no sync."""
     _check_image_tensor(left, "left")
     _check_image_tensor(right, "right")
+    if left.dtype != torch.uint8 or right.dtype != torch.uint8:  # (the kernel reads bytes; apply_lr does wide types on the host)
+        raise TypeError(f"anaglyph_tensors: uint8 images only, not {left.dtype} / {right.dtype}")
     if left.shape != right.shape or left.shape[2] != 3 or left.device != right.device:
         raise ValueError("anaglyph needs two (H, W, 3) uint8 tensors of the same shape on one device")
     h, w = int(left.shape[0]), int(left.shape[1])
@@ -877,7 +953,17 @@ def apply_lr(
     sbs = apply_lr_tensors(transformer, lt, rt, size_output=size_output, interpolation=interpolation,
                            boarder_mode=boarder_mode, boarder_value=boarder_value,
                            radius=_radius_for_pair(radius, transformer, left, right))
-    if merge:
+    if merge and sbs.dtype != torch.uint8:
+        # 16-bit / float32: the reference's own NumPy expression (remapper.py:485-497) on the host copy (the anaglyph kernel is 8-bit)
+        w = size_output[0]
+        host = sbs.cpu().numpy()
+        images = [host[:, :w], host[:, w:]]
+        colors = [(0, 128, 255), (255, 128, 0)]
+        combine = np.mean(images[0], axis=-1)[..., None] * np.array(colors[0]).reshape([1] * (images[0].ndim - 1) + [3]) + (
+            np.mean(images[1], axis=-1)[..., None] * np.array(colors[1]).reshape([1] * (images[1].ndim - 1) + [3]))
+        combine /= 255
+        combine = _io.draw_anaglyph_labels(combine)
+    elif merge:
         # red/cyan anaglyph of the two halves, on the device (remapper.py:485-497); the labels need
         # cv2.putText and are drawn on the host copy when cv2 is importable (:498-516)
         w = size_output[0]
