@@ -317,6 +317,52 @@ int v1c_build_itab(int interp, int16_t* out);
  * INTER_CUBIC (1024*4*4) or INTER_LANCZOS4 (1024*8*8).  Host-only; `out` is a HOST buffer.                                 */
 int v1c_build_ftab(int interp, float* out);
 
+/* ---- feature matching of the two eyes (--automatch devfm; replaces the cv2.AKAZE + BFMatcher front end of remapper.py:194-248) --
+ * NOT AKAZE: a single-scale, oriented binary-feature pipeline whose every stage is integer arithmetic, so that its keypoints,
+ * descriptors and matches are reproducible bit for bit (INTEGRATION.md section 5 states the contract; tests/feat_ref.py restates it).
+ * Defaults in brackets.                                                                                                          */
+typedef struct v1c_feat_params {
+    double  scale;          /* working scale s in (0, 1]: working size (int(w * s), int(h * s)), block-mean resampling [1]      */
+    double  radius;         /* image-circle radius in ORIGINAL pixels (what get_radius_smart resolves), centre (w / 2, h / 2)   */
+    int32_t fast_threshold; /* FAST-9 score threshold, 1..255 [20]                                                             */
+    int32_t margin;         /* keypoints lie within radius * s - margin working pixels of the centre [19]                      */
+    int32_t cell;           /* grid cell in working pixels, 8..64 [32]                                                         */
+    int32_t per_cell;       /* keypoints kept per cell, 1..4 [2]                                                                */
+    int32_t max_keypoints;  /* N_max, 1..2^20 [8192]: the capacity of kp_out / desc_out                                          */
+    int32_t max_distance;   /* match: largest Hamming distance kept, 0..256 [64]                                                 */
+    int32_t ratio_num;      /* match: kept iff ratio_den * d1 <= ratio_num * d2 [3 / 4]                                          */
+    int32_t ratio_den;
+} v1c_feat_params;
+
+typedef struct v1c_feat_kp {
+    int32_t x, y;           /* working-scale pixel                                                                              */
+    int32_t score;          /* FAST-9 score                                                                                     */
+    int32_t bin;            /* orientation sector 0..29 (12 degrees each)                                                       */
+    int32_t src_x2, src_y2; /* twice the centre of the keypoint's source block in original pixels: c0 + c1 - 1, r0 + r1 - 1       */
+} v1c_feat_kp;
+
+/* Keypoints and 32-byte descriptors of one uint8 image (device pointer, (h, w, cn), cn 1 / 3 / 4, BGR(A) order).  Writes at most
+ * max_keypoints records to kp_out and descriptors to desc_out (device; desc_out 8-byte aligned), cell-major, and their number to
+ * *count_out_dev (device).  Enqueues its work on `stream` (scratch allocated stream-ordered) and waits for none of it, with two host-side
+ * exceptions: the first call on a device uploads the sampling pattern with a blocking copy, and every call copies its host-computed
+ * tables (block boundaries, qualifying columns per row: 4 (w' + h') + 8 h' bytes) from pageable memory, a copy that HIP may
+ * finish before returning.  Rows and columns within 16 working pixels of the image edge never hold a keypoint, whatever the radius
+ * and the margin.  V1C_E_INVALID for cn outside
+ * {1, 3, 4}, s outside (0, 1], a working image smaller than 33 x 33, an empty circle, NULL pointers, parameters out of range.     */
+int v1c_feat_detect(int device, void* stream, const uint8_t* img, int h, int w, int64_t pitch, int cn,
+                    const v1c_feat_params* params, v1c_feat_kp* kp_out, uint8_t* desc_out, int32_t* count_out_dev);
+
+/* Brute-force Hamming match of n_a descriptors against n_b (device, 16-byte aligned), both directions.  Pair (i, j) is kept iff i and j
+ * are each other's best (ties: the lowest index), d1 <= max_distance and ratio_den * d1 <= ratio_num * d2 (d2: the second-best
+ * distance of i's row; with a single candidate only the max_distance test applies).  pairs_out (i, j) int32 pairs and dist_out in
+ * query order, at most min(n_a, n_b); their number to *count_out_dev.  Launch-only.                                              */
+int v1c_feat_match(int device, void* stream, const uint8_t* desc_a, int n_a, const uint8_t* desc_b, int n_b,
+                   const v1c_feat_params* params, int32_t* pairs_out, int32_t* dist_out, int32_t* count_out_dev);
+
+/* The rotated sampling pattern the descriptors read: 30 sectors x 256 pairs x (px, py, qx, qy) int8 offsets (30 720 bytes).
+ * Host-only; `out` is a HOST buffer.                                                                                            */
+int v1c_feat_pattern(int8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ from .chain import (
 )
 from .remapper import (anaglyph_tensors, apply, apply_lr, apply_lr_tensors, auto_radius_tensor, get_map, remap_tensors,
                        remap_tensors_auto)
+from .features import detect, match, match_points_device
 from .sharding import remap_sharded
 
 __all__ = [
@@ -41,4 +42,8 @@ __all__ = [
     "remap_tensors_auto",
     "auto_radius_tensor",
     "remap_sharded",
+    # feature matching of the two eyes (--automatch devfm)
+    "detect",
+    "match",
+    "match_points_device",
 ]

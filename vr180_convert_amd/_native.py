@@ -22,6 +22,7 @@ SYMBOLS = [
     "v1c_get_radius", "v1c_get_radius_async", "v1c_build_itab", "v1c_anaglyph", "v1c_fused_cache_size", "v1c_plan_last_launch",
     "v1c_plan_release_captures", "v1c_plan_run_auto", "v1c_plan_run_auto_images",
     "v1c_plan_create_ex", "v1c_remap_lut_ex", "v1c_build_ftab",
+    "v1c_feat_detect", "v1c_feat_match", "v1c_feat_pattern",
 ]
 
 
@@ -68,6 +69,12 @@ def lib() -> C.CDLL:
         L.v1c_plan_create_ex.argtypes = [C.POINTER(vp), i32, C.POINTER(_abi.Chain), i32, i32, i32, i32, i32, i32, i32, i32, vp]
         L.v1c_remap_lut_ex.argtypes = [i32, vp, vp, i32, i32, i64, i32, i32, vp, i32, i32, i64, vp, vp, i64, i32, i32, vp]
         L.v1c_build_ftab.argtypes = [i32, vp]
+    except AttributeError:  # (an older build behind V1C_LIB)
+        pass
+    try:
+        L.v1c_feat_detect.argtypes = [i32, vp, vp, i32, i32, i64, i32, vp, vp, vp, vp]
+        L.v1c_feat_match.argtypes = [i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
+        L.v1c_feat_pattern.argtypes = [vp]
     except AttributeError:  # (an older build behind V1C_LIB)
         pass
     L.v1c_plan_run.argtypes = [vp, vp, C.POINTER(_abi.Unit), i32]

@@ -2,9 +2,10 @@
 
 ``rotation_match`` / ``rotation_match_robust`` (reference remapper.py:93-191) produce the per-pair
 quaternions that ``remap_tensors(..., rotations=...)`` consumes (BASELINE config 5).  They are one
-3x3 correlation and one symmetric 4x4 eigenproblem on the host.  Feature detection and matching
-(``match_points``, remapper.py:194-248: cv2.AKAZE + BFMatcher) needs OpenCV and is not mirrored;
-everything downstream of the matched points is: ``match_lr`` (points -> unit rays through the
+3x3 correlation and one symmetric 4x4 eigenproblem on the host.  The reference's feature detection and
+matching (``match_points``, remapper.py:194-248: cv2.AKAZE + BFMatcher) needs OpenCV (``calibration_cv``);
+``features.match_points_device`` is this engine's own matcher on the GPU (``--automatch devfm``: not AKAZE,
+bit-exact against a NumPy restatement).  Everything downstream of the matched points is mirrored: ``match_lr`` (points -> unit rays through the
 decoder's inverse, remapper.py:251-321), the rotation fit, and ``calibration_rotators`` (the
 pseudo-half quaternions the CLI inserts per eye, cli.py:308-319).
 """

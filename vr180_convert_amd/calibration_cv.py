@@ -6,6 +6,9 @@
 * ``draw_match_image`` -- the ``--savematch`` picture: 100 sampled inlier matches side by side (cli.py:299-304, 362-365);
 * ``write_vr180_xmp`` -- the ``xmp`` command's Google VR180 photo metadata (GPano / GImage XMP, cli.py:439-540).
 
+``--automatch devfm`` (``features.match_points_device``) is the engine's own feature matcher on the GPU and needs none of this
+module: it is not AKAZE and does not reproduce ``match_points``' output, but returns the same 7-tuple.
+
 None of them is on the remap path and none has arithmetic of its own to restate: they hand images to ``cv2`` / ``libxmp`` and results
 on.  The engine's GPU image ships neither library, so every function raises ``OptionalDependencyMissing`` -- with the package to
 install -- when its import fails; the CLI turns that into a usage error.  ``tests/test_cli.py`` drives all four through stand-in

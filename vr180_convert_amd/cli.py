@@ -6,7 +6,8 @@ itself happens on the MI355X through ``apply`` / ``apply_lr``.
 What is OpenCV or libxmp from end to end -- AKAZE feature matching (``--automatch fm[scale]``, cli.py:255-262, with ``--savematch``),
 the point-picking window (``--automatch gui[n]``, cli.py:82-113) and the ``xmp`` command (cli.py:439-540) -- lives in
 ``calibration_cv.py`` behind lazy imports: with the library installed the options work as in the reference, without it they report
-which package is missing (the GPU image of this engine ships neither); explicit points (``--automatch "x,y;x,y;..."``) need nothing.
+which package is missing (the GPU image of this engine ships neither); explicit points (``--automatch "x,y;x,y;..."``) need nothing,
+and neither does ``--automatch devfm[scale]``: the engine's own feature matcher on the GPU (``features.py``; not AKAZE).
 """
 from __future__ import annotations
 
@@ -133,7 +134,16 @@ def calibrated_pair(transformer: Any, automatch: str, left: Path, right: Path, r
     ``--savematch`` wants 100 of the surviving matches drawn)."""
     head, tail = split_at_first_encoder(transformer)
     matched = None
-    if automatch.startswith("fm") or automatch.startswith("gui"):
+    if automatch.startswith("devfm"):
+        # feature matching on the device (features.py): no OpenCV; outlier-ridden like fm, hence the robust fit too
+        from . import features as _feat
+
+        scale = _option_number(automatch, "devfm", r"([\d\.]+)", 1)
+        if not 0 < scale <= 1:
+            raise typer.BadParameter(f"--automatch {automatch}: the working scale must lie in (0, 1], e.g. devfm0.5")
+        matched = _feat.match_points_device(_io.imread(left), _io.imread(right), scale=scale, radius=radius)
+        points_l, points_r = matched[0], matched[1]
+    elif automatch.startswith("fm") or automatch.startswith("gui"):
         from . import calibration_cv as _cvx
 
         try:
@@ -155,7 +165,7 @@ def calibrated_pair(transformer: Any, automatch: str, left: Path, right: Path, r
     vl, vr = match_lr(tail, points_l, points_r, in_paths=[left, right], radius=radius)
     if matched is not None:
         q, discarded = rotation_match_robust(vl, vr)
-        if match_image_path is not None:
+        if match_image_path is not None and automatch.startswith("fm"):
             from . import calibration_cv as _cvx
 
             _, _, kp_l, kp_r, matches, small_l, small_r = matched
@@ -196,8 +206,9 @@ def lr(
         help="Autosearch timestamp calibration (right timestamp -= this) (in seconds)")] = 0.0,
     swap: Annotated[bool, typer.Option(help="Swap left and right images as well as transformer, etc.")] = False,
     name_unique: Annotated[bool, typer.Option(help="Make output name unique")] = False,
-    automatch: Annotated[str, typer.Option(help='Calibrate rotation. e.g. "0,0;0,0;1,1;1,1", "gui[n]" (click n point pairs) or '
-                                                 '"fm[scale]" (AKAZE feature matching); the last two need OpenCV')] = "",
+    automatch: Annotated[str, typer.Option(help='Calibrate rotation. e.g. "0,0;0,0;1,1;1,1", "gui[n]" (click n point pairs), '
+                                                 '"fm[scale]" (AKAZE feature matching) -- these two need OpenCV -- or "devfm[scale]" '
+                                                 '(feature matching on the GPU, no OpenCV; not AKAZE)')] = "",
     savematch: Annotated[bool, typer.Option(help="Save the match image <out>.match<ext> (only with automatch=fm)")] = False,
 ) -> None:
     """Remap a pair of fisheye images to a pair of SBS equirectangular images."""

@@ -37,6 +37,14 @@ static int fail(int code, const std::string& msg)
     return code;
 }
 
+// the same for the entry points of other files (feat.hip)
+namespace v1c {
+int set_error(int code, const std::string& msg)
+{
+    return fail(code, msg);
+}
+}  // namespace v1c
+
 #define HIP_TRY(expr)                                                                                   \
     do {                                                                                                \
         hipError_t _e = (expr);                                                                         \
