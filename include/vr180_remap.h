@@ -363,6 +363,35 @@ int v1c_feat_match(int device, void* stream, const uint8_t* desc_a, int n_a, con
  * Host-only; `out` is a HOST buffer.                                                                                            */
 int v1c_feat_pattern(int8_t* out);
 
+/* ---- PNG encoding of a device image (INTEGRATION.md section 6 states the stream; tests/png_ref.py restates it) ------------------
+ * The image's filtered scanlines, cut into bands of band_rows rows, every band deflated from an empty window as ONE dynamic Huffman
+ * block of literals and distance-1 matches (zlib's Z_RLE class) closed by an empty stored block, or as stored blocks where that is
+ * smaller.  The caller wraps the concatenated band segments into a zlib stream and a PNG container (_png.assemble).               */
+#define V1C_PNG_FILTER_UP    2
+#define V1C_PNG_FILTER_PAETH 4
+
+typedef struct v1c_png_band {
+    uint32_t row0, row1;    /* the band's rows [row0, row1)                                                                      */
+    uint64_t offset, size;  /* its segment of out_host                                                                           */
+    uint32_t adler32;       /* of its scanline bytes                                                                             */
+    uint32_t stored;        /* 1: stored blocks, 0: one dynamic block + the empty stored block                                   */
+} v1c_png_band;
+
+/* Bytes the band segments of an (h, w, cn) image of `depth` (V1C_DEPTH_8U / _16U) can need: every band as stored blocks (scanline
+ * bytes + 5 per started 65535) + 8 per band.  Host-only.  0 for invalid arguments.                                              */
+uint64_t v1c_png_bound(int h, int w, int cn, int depth, int band_rows);
+
+/* Encodes the device image img ((h, w, cn) in cv2 channel order, cn 1 / 3 / 4, uint8 or uint16, row pitch in BYTES) on `stream`,
+ * SYNCHRONISES the stream (twice: once for the histograms the host builds the codes from, once at the end) and leaves the band
+ * segments back to back in out_host (HOST memory of `capacity` >= v1c_png_bound bytes; page-locked recommended), one v1c_png_band
+ * per band in bands_out (host, ceil(h / band_rows) records), their number in *n_bands_out and the total in *size_out.  The result
+ * is a pure function of the pixels and the parameters.  V1C_E_INVALID before any device call for cn, depth, filter, sizes < 1 or
+ * above 2^20, a band above 2^31 - 1 scanline bytes, NULL pointers, capacity below the bound, pitch < row bytes, a 16-bit image
+ * whose pointer or pitch is odd.                                                                                                */
+int v1c_png_deflate(int device, void* stream, const void* img, int h, int w, int64_t pitch, int cn, int depth, int filter,
+                    int band_rows, uint8_t* out_host, uint64_t capacity, v1c_png_band* bands_out, int32_t* n_bands_out,
+                    uint64_t* size_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ from .chain import (
 from .remapper import (anaglyph_tensors, apply, apply_lr, apply_lr_tensors, auto_radius_tensor, get_map, remap_tensors,
                        remap_tensors_auto)
 from .features import detect, match, match_points_device
+from .png_device import encode_png_tensor, imwrite_tensor
 from .sharding import remap_sharded
 
 __all__ = [
@@ -46,4 +47,7 @@ __all__ = [
     "detect",
     "match",
     "match_points_device",
+    # PNG files of device-resident results, deflated on the device (device_png=True / --device-png)
+    "encode_png_tensor",
+    "imwrite_tensor",
 ]

@@ -23,6 +23,7 @@ SYMBOLS = [
     "v1c_plan_release_captures", "v1c_plan_run_auto", "v1c_plan_run_auto_images",
     "v1c_plan_create_ex", "v1c_remap_lut_ex", "v1c_build_ftab",
     "v1c_feat_detect", "v1c_feat_match", "v1c_feat_pattern",
+    "v1c_png_bound", "v1c_png_deflate",
 ]
 
 
@@ -75,6 +76,12 @@ def lib() -> C.CDLL:
         L.v1c_feat_detect.argtypes = [i32, vp, vp, i32, i32, i64, i32, vp, vp, vp, vp]
         L.v1c_feat_match.argtypes = [i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
         L.v1c_feat_pattern.argtypes = [vp]
+    except AttributeError:  # (an older build behind V1C_LIB)
+        pass
+    try:
+        L.v1c_png_bound.argtypes = [i32, i32, i32, i32, i32]
+        L.v1c_png_bound.restype = C.c_uint64
+        L.v1c_png_deflate.argtypes = [i32, vp, vp, i32, i32, i64, i32, i32, i32, i32, vp, C.c_uint64, vp, vp, vp]
     except AttributeError:  # (an older build behind V1C_LIB)
         pass
     L.v1c_plan_run.argtypes = [vp, vp, C.POINTER(_abi.Unit), i32]

@@ -7,9 +7,13 @@ own thread (zlib releases the GIL) as a raw deflate segment that ends on a byte 
 the segments are concatenated into ONE valid zlib stream (header + segments + Adler-32 of all scanlines): any PNG
 reader decodes it, pixels are stored losslessly as always.  The GPU image has no device-side codec (no rocJPEG /
 nvJPEG equivalent, no torchvision), so this is the file path; ``.npy`` is the codec-free one (_io.py).
+
+``assemble`` builds the same container around band segments that were deflated elsewhere: ``png_device.py`` deflates
+device-resident results on the GPU (``device_png=True``; larger files, no host deflate) and hands its stream here.
 """
 from __future__ import annotations
 
+import functools
 import os
 import struct
 import zlib
@@ -44,6 +48,98 @@ def _adler32_combine(a1: int, a2: int, len2: int) -> int:
     if s2 >= base:
         s2 -= base
     return s1 | (s2 << 16)
+
+
+def _gf2_times(mat: list[int], vec: int) -> int:
+    out, i = 0, 0
+    while vec:
+        if vec & 1:
+            out ^= mat[i]
+        vec >>= 1
+        i += 1
+    return out
+
+
+def _gf2_matmul(a, b) -> list[int]:
+    return [_gf2_times(a, v) for v in b]
+
+
+@functools.lru_cache(maxsize=64)
+def _crc32_zeros_operator(nbytes: int) -> tuple:
+    """the 32 x 32 matrix over GF(2) that takes a CRC-32 register over ``nbytes`` zero bytes (zlib's crc32_combine builds the same
+    operator by repeated squaring)"""
+    power = [0xEDB88320] + [1 << n for n in range(31)]  # one zero bit
+    for _ in range(3):
+        power = _gf2_matmul(power, power)               # one zero byte
+    out = [1 << n for n in range(32)]
+    while nbytes:
+        if nbytes & 1:
+            out = _gf2_matmul(power, out)
+        nbytes >>= 1
+        if nbytes:
+            power = _gf2_matmul(power, power)
+    return tuple(out)
+
+
+def crc32_combine(crc1: int, crc2: int, len2: int) -> int:
+    """CRC-32 of a concatenation from the checksums of its two parts (zlib's crc32_combine)"""
+    if len2 <= 0:
+        return crc1 & 0xFFFFFFFF
+    return (_gf2_times(_crc32_zeros_operator(len2), crc1) ^ crc2) & 0xFFFFFFFF
+
+
+_CRC_STEP = 1 << 20
+
+
+def _crc32_parallel(parts: list, threads: int) -> int:
+    """CRC-32 of the concatenation of ``parts`` (bytes-like).  Whole pieces of _CRC_STEP bytes of a large part are summed on a
+    thread pool (zlib.crc32 releases the GIL) and combined with ONE cached operator; everything else runs through zlib.crc32's
+    running value."""
+    crc = 0
+    for part in parts:
+        mv = memoryview(part)
+        full = len(mv) // _CRC_STEP if threads > 1 and len(mv) >= 4 * _CRC_STEP else 0
+        if full:
+            with ThreadPoolExecutor(max_workers=threads) as pool:
+                sums = list(pool.map(zlib.crc32, [mv[o * _CRC_STEP:(o + 1) * _CRC_STEP] for o in range(full)]))
+            op = _crc32_zeros_operator(_CRC_STEP)
+            for s in sums:
+                crc = _gf2_times(op, crc) ^ s
+        crc = zlib.crc32(mv[full * _CRC_STEP:], crc)
+    return crc & 0xFFFFFFFF
+
+
+def assemble_parts(segments: Any, bands: list, *, width: int, height: int, channels: int, bit_depth: int = 8, filter_type: int = 2,
+                   threads: int | None = None) -> list:
+    """``assemble`` as a list of buffers to write one after the other (the stream itself is not copied)"""
+    seg = memoryview(segments).cast("B")
+    stride = 1 + width * channels * (bit_depth // 8)
+    total = 0
+    adler = 1
+    index = struct.pack(">BBI", 1, filter_type, len(bands))
+    for r0, r1, off, size, ad in bands:
+        if off != total:
+            raise ValueError("band segments must lie back to back")
+        adler = _adler32_combine(adler, ad, (r1 - r0) * stride)
+        index += struct.pack(">III", r0, r1, 2 + off)
+        total += size
+    head, tail = b"\x78\x01", b"\x01\x00\x00\xff\xff" + struct.pack(">I", adler & 0xFFFFFFFF)
+    body = seg[:total]
+    nthreads = threads or min(32, os.cpu_count() or 1)
+    crc = _crc32_parallel([b"IDAT" + head, body, tail], nthreads)
+    ihdr = struct.pack(">IIBBBBB", width, height, bit_depth, {1: 0, 3: 2, 4: 6}[channels], 0, 0, 0)
+    return [_SIGNATURE + _chunk(b"IHDR", ihdr) + _chunk(_INDEX_CHUNK, index) + struct.pack(">I", 2 + total + 9) + b"IDAT" + head, body,
+            tail + struct.pack(">I", crc) + _chunk(b"IEND", b"")]
+
+
+def assemble(segments: Any, bands: list, **kw: Any) -> bytes:
+    """The PNG file around band segments that were deflated elsewhere (the device encoder, ``png_device.encode_png_tensor``):
+    ``segments`` holds the bands' raw-deflate segments back to back (every one from an empty window, ending on a byte boundary, none
+    final), ``bands`` one ``(row0, row1, offset, size, adler32)`` per band with the Adler-32 of the band's scanline bytes; keywords
+    ``width``, ``height``, ``channels``, ``bit_depth`` [8], ``filter_type`` [2], ``threads``.  Adds the zlib header, one empty final
+    stored block, the combined Adler-32, and the container ``encode`` writes: IHDR, the band directory, one IDAT (its CRC-32 summed
+    in parts on a thread pool), IEND."""
+    return b"".join(assemble_parts(segments, bands, **kw))
 
 
 def _to_png_order(dst: np.ndarray, a: np.ndarray) -> None:

@@ -210,6 +210,8 @@ def lr(
                                                  '"fm[scale]" (AKAZE feature matching) -- these two need OpenCV -- or "devfm[scale]" '
                                                  '(feature matching on the GPU, no OpenCV; not AKAZE)')] = "",
     savematch: Annotated[bool, typer.Option(help="Save the match image <out>.match<ext> (only with automatch=fm)")] = False,
+    device_png: Annotated[bool, typer.Option("--device-png", help="Deflate .png results on the GPU (larger files, no host codec "
+                                                                   "time); other formats and --merge are written by the host")] = False,
 ) -> None:
     """Remap a pair of fisheye images to a pair of SBS equirectangular images."""
     from .remapper import apply_lr
@@ -236,7 +238,8 @@ def lr(
         chain = calibrated_pair(chain, automatch, left_path, right_path, radius_, match_image)
         LOG.info(f"Automatched transformer: {chain}")
     apply_lr(chain, left_path=left_path, right_path=right_path, out_path=out, radius=radius_, size_output=parse_size(size),
-             interpolation=interp, boarder_mode=border, boarder_value=border_value, merge=merge)
+             interpolation=interp, boarder_mode=border, boarder_value=border_value, merge=merge,
+             **({"device_png": True} if device_png else {}))
 
 
 @app.command()
@@ -249,6 +252,8 @@ def s(
     boarder_mode: Annotated[str, typer.Option(help="Border mode (cv2 name)")] = "border_constant",
     boarder_value: int = 0,
     radius: Annotated[str, typer.Option(help="Radius of the fisheye image: a number, 'auto' or 'max'")] = "auto",
+    device_png: Annotated[bool, typer.Option("--device-png", help="Deflate .png results on the GPU (larger files, no host codec "
+                                                                   "time); other formats and --merge are written by the host")] = False,
 ) -> None:
     """Remap fisheye images to equirectangular images (one shared map for all of them)."""
     from .remapper import apply
@@ -263,7 +268,8 @@ def s(
         out_paths = [out_path]
     apply(parse_transformer(transformer), in_paths=list(in_paths), out_paths=out_paths, radius=parse_radius(radius),
           size_output=parse_size(size), interpolation=_flag(interpolation, _INTERPOLATIONS, "inter_", "interpolation"),
-          boarder_mode=_flag(boarder_mode, _BORDERS, "border_", "border mode"), boarder_value=boarder_value)
+          boarder_mode=_flag(boarder_mode, _BORDERS, "border_", "border mode"), boarder_value=boarder_value,
+          **({"device_png": True} if device_png else {}))
 
 
 @app.command()

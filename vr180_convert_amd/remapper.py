@@ -686,6 +686,7 @@ def apply(
     boarder_value: int | tuple[int, int, int] = 0,
     radius: float | Literal["auto", "max"] = "auto",
     device: Any = None,
+    device_png: bool = False,
 ) -> Sequence[NDArray[np.uint8]]:
     """Apply transformer to images (reference remapper.py:324-403).
 
@@ -734,8 +735,19 @@ def apply(
         results = [d.cpu().numpy() for d in dsts]
         results = [r[..., 0] if np.asarray(im).ndim == 2 else r for r, im in zip(results, images)]
     if out_paths_ is not None:
-        _io.imwrite_many(list(out_paths_)[: len(results)],
-                         [image.cpu().numpy() if isinstance(image, torch.Tensor) else image for image in results])
+        paths = list(out_paths_)[: len(results)]
+        if device_png:
+            from . import png_device
+
+            on_dev = [png_device.eligible(q, d) for q, d in zip(paths, dsts)]
+            for q, d, ok in zip(paths, dsts, on_dev):
+                if ok:
+                    png_device.imwrite_tensor(q, d)
+            keep = [i for i, ok in enumerate(on_dev) if not ok]
+            paths, results_ = [paths[i] for i in keep], [results[i] for i in keep]
+        else:
+            results_ = results
+        _io.imwrite_many(paths, [image.cpu().numpy() if isinstance(image, torch.Tensor) else image for image in results_])
     return results
 
 
@@ -938,9 +950,13 @@ def apply_lr(
     radius: float | Literal["auto", "max"] = "auto",
     merge: bool = False,
     device: Any = None,
+    device_png: bool = False,
 ) -> None:
     """Apply transformer to a pair of images and save them side by side (reference
-    remapper.py:406-520).  ``left_path == right_path`` means one file holding both eyes."""
+    remapper.py:406-520).  ``left_path == right_path`` means one file holding both eyes.
+
+    ``device_png=True``: a ``.png`` ``out_path`` of a uint8 / uint16 side-by-side result is deflated on the device
+    (png_device.imwrite_tensor) and the raw result is not copied to the host; ``merge=True`` and other formats take the host route."""
     if isinstance(left_path, (str, Path)) and isinstance(right_path, (str, Path)) and left_path == right_path:
         image = _io.imread(left_path)
         left_path = image[:, : image.shape[1] // 2]
@@ -969,6 +985,13 @@ def apply_lr(
         w = size_output[0]
         combine = _io.draw_anaglyph_labels(anaglyph_tensors(sbs[:, :w], sbs[:, w:]).cpu().numpy())
     else:
+        if device_png and out_path is not None:
+            from . import png_device
+
+            if png_device.eligible(out_path, sbs):
+                png_device.imwrite_tensor(out_path, sbs)
+                LOG.info(f"Saved to {Path(out_path).absolute()}")
+                return
         combine = sbs.cpu().numpy()
     if out_path is not None:
         _io.imwrite(out_path, combine)
