@@ -353,3 +353,57 @@ def test_cli_flag_reaches_apply_and_apply_lr(tmp_path, monkeypatch):
     assert run(cli.app, ["s", str(img), *base, "--device-png", "--out-path", str(tmp_path / "o.png")]).exit_code == 0
     assert run(cli.app, ["s", str(img), *base, "--out-path", str(tmp_path / "o.png")]).exit_code == 0
     assert seen == [("lr", True), ("lr", None), ("s", True), ("s", None)]
+
+
+# ---- the boundary images the GPU half runs (tests/png_cases.py): generators and restatement proven on the host first --------------
+import png_cases as PC  # noqa: E402
+
+EDGE_PARAMS = [(name, f) for name in PC.shared_cases() for f in ("up", "paeth")]
+
+
+def test_from_filtered_gives_the_filtered_bytes():
+    rng = _rng(21)
+    f = PC.run_plane(rng, 9, 300)
+    assert np.array_equal(R.scanlines(PC.from_filtered(f), "up"), f)
+    f = PC.fibonacci_row(rng, 21)
+    assert f.shape == (1, 28656) and np.array_equal(R.scanlines(PC.from_filtered(f), "up"), f)
+    assert sorted(np.bincount(f.reshape(-1))[np.bincount(f.reshape(-1)) > 0].tolist()) == sorted(PC._fib(21))
+
+
+def test_edge_cases_sit_on_the_boundaries_they_are_for():
+    """What the list must contain (both filters over all of it), and the band sizes that name the kernels' boundaries."""
+    cases = PC.shared_cases()
+    stats = {(n, f): PC.band_stats(img, f, rows) for n, (img, rows) in cases.items() for f in ("up", "paeth")}
+    coded = [b for s in stats.values() for b in s if not b["stored"]]
+    assert any(b["max_len"] == 15 for b in coded)                      # a code with a 15-bit length
+    assert any(b["depth"] > 15 for b in coded)                         # package-merge engages
+    lengths = set().union(*(b["matches"] for b in coded))
+    assert min(lengths) == 4 and max(lengths) == 255
+    for lo, hi in ((4, 10), (11, 130), (131, 255)):
+        assert any(lo <= v <= hi for v in lengths), (lo, hi)
+    assert {62, 63, 64, 65, 66, 127, 128, 129, 250, 255} <= lengths  # runs of 63 ... 67, 128 ... 130, 251, 256 and more bytes: across the lane steps
+    assert any(len({b["stored"] for b in s}) == 2 for s in stats.values())  # stored and coded bands in one file
+    size = {n: [b["nbytes"] for b in stats[(n, "up")]] for n in cases}
+    assert size["runs_stride256_8rows"] == [2048] * 3 and size["runs_stride257_1row"] == [257] * 7
+    assert size["runs_16384"] == [64 * 256] and size["runs_16448"] == [65 * 256 - 192]
+    assert size["runs_65536"] == [256 * 256] and size["runs_65792"] == [257 * 256 - 0] and size["runs_65792_two_values"][0] == 65792
+    assert size["fib21_one_row"] == [28656] and size["fib24_stride602"] == [64 * 602] * 2
+    for n in (65535, 65536, 65537, 131070, 131071):
+        assert size[f"noise_{n}"] == [n] and all(b["stored"] for b in stats[(f"noise_{n}", "up")] + stats[(f"noise_{n}", "paeth")])
+    assert [b["stored"] for b in stats[("noise_then_runs", "up")]] == [True, False]
+    assert {cases[n][0].dtype.itemsize * cases[n][0].shape[2] for n in cases} == {1, 2, 3, 4, 6, 8}  # every bytes-per-pixel the kernels have
+    for n in ("runs_gray16_16448", "runs_bgra16_65792", "runs_bgra_65792", "runs_bgr_16384"):
+        assert size[n][0] in (16384, 16448, 65792) and not stats[(n, "up")][0]["stored"]
+
+
+@pytest.mark.parametrize("name,filter", EDGE_PARAMS)
+def test_edge_cases_product_host_code_equals_restatement(png_emul, name, filter):
+    img, rows = PC.shared_cases()[name]
+    want, wbands, wfile = PC.reference(name, filter)
+    got, bands = _emul(png_emul, img, filter, rows)
+    assert bands == wbands  # (row0, row1, offset, size, adler32, stored) of every band
+    assert got == want
+    check_file(wfile, img, filter, rows)
+    png = _png.assemble(got, [b[:5] for b in bands], width=img.shape[1], height=img.shape[0], channels=img.shape[2],
+                        bit_depth=8 * img.dtype.itemsize, filter_type=R.FILTERS[filter])
+    assert png == wfile

@@ -339,3 +339,60 @@ def test_shared_plan_memo_keys_every_unit(monkeypatch):
         remapper.clear_caches()
     assert len(plans) == 3
     assert sorted(len(p.runs) for p in plans.values()) == [1, 1, 5]
+
+
+# ---- the adversarial cases the GPU half runs (tests/wide_cases.py): generators and restatement proven on the host first ------------
+@pytest.mark.parametrize("dtype", [np.uint16, np.float32])
+@pytest.mark.parametrize("interp", [0, 1, 2, 3, 4])
+def test_wide_cases_host_sampler_equals_restatement(product_lib, wide_emul, dtype, interp):
+    """Special-valued maps, 1-pixel sources, pitched and odd-offset views, extreme float32 pixels: the whole buffers are compared, so a
+    store outside the destination view shows as well."""
+    import wide_cases as WC
+
+    ftab = product_ftab(product_lib, interp) if interp in (R.INTER_CUBIC, R.INTER_LANCZOS4) else None
+    n = 0
+    for c in WC.cases(dtype, interp):
+        sbuf = WC.place(c.src_view, c.src)
+        dbuf = WC.place(c.dst_view, c.fill)
+        want = dbuf.copy()
+        WC.window(c.dst_view, want, c.fill.shape)[...] = R.remap(c.src, c.xm, c.ym, c.interp, c.border, c.bv, dst=c.fill)
+        cval = product_cval(wide_emul, DEPTH[dtype], c.bv)
+        isz = sbuf.dtype.itemsize
+        hs, ws, cn = c.src.shape
+        ho, wo = c.xm.shape
+        rc = wide_emul.wide_remap_host(sbuf.ctypes.data + c.src_view.offset * isz, hs, ws, c.src_view.pitch * isz, cn, DEPTH[dtype],
+                                       dbuf.ctypes.data + c.dst_view.offset * isz, ho, wo, c.dst_view.pitch * isz, c.xm.ctypes.data,
+                                       c.ym.ctypes.data, c.interp, c.border, cval.ctypes.data, None if ftab is None else ftab.ctypes.data)
+        assert rc == 0
+        assert WC.same(dbuf, want), (str(c), WC.ndiff(dbuf, want))
+        n += 1
+    assert n == 6 * 3 * WC.ROUNDS
+
+
+def test_wide_cases_cover_what_they_are_for():
+    import test_gpu_wide
+    import wide_cases as WC
+
+    assert all(v in WC.BORDER_VALUES for v in test_gpu_wide.BVS)
+    for dtype in WC.DTYPES:
+        for interp in WC.INTERPS:
+            cs = list(WC.cases(dtype, interp))
+            assert {(c.border, c.cn) for c in cs} == {(b, n) for b in WC.BORDERS for n in WC.CNS}
+            assert {c.xm.shape[1] for c in cs} == set(WC.OUT_WIDTHS) and {c.xm.shape[0] for c in cs} == set(WC.OUT_HEIGHTS)
+            assert {c.dst_view.kind for c in cs} == set(WC.VIEWS) and {c.src_view.kind for c in cs} == set(WC.VIEWS)
+            assert {c.src_kind for c in cs} == set(WC.SRC_KINDS) and {c.map_kind for c in cs} == set(WC.MAP_KINDS)
+            assert {c.map_pad for c in cs} == set(WC.MAP_PADS)
+            if dtype == np.uint16:
+                # a destination row that is 2-byte aligned only -- by the view's offset, and by an odd pitch behind an aligned offset
+                # -- under a full lane (4 pixels written), for cn 1 and 3 (cn 4: an odd offset alone does it)
+                odd = [c for c in cs if c.dst_view.kind == "pitched-odd" and c.xm.shape[1] >= 4]
+                assert {c.cn for c in odd} == {1, 3, 4}
+                assert any(c.dst_view.pitch % 2 for c in cs if c.cn in (1, 3) and c.xm.shape[0] > 1)
+            else:
+                ext = [c for c in cs if c.extremes]
+                assert len(cs) // 4 <= len(ext) <= len(cs) // 2
+                px = np.concatenate([c.src.reshape(-1) for c in ext])
+                assert np.isnan(px).any() and np.isinf(px).any() and (np.abs(px) > 3e38).any() and (np.signbit(px) & (px == 0)).any()
+                assert ((px != 0) & (np.abs(px) < np.float32(1.1754944e-38))).any()  # denormals
+    a, b = list(WC.cases(np.float32, 4)), list(WC.cases(np.float32, 4))
+    assert all(np.array_equal(x.xm, y.xm, equal_nan=True) and np.array_equal(x.src, y.src, equal_nan=True) for x, y in zip(a, b))

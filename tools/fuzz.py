@@ -7,6 +7,18 @@ and destination views (dword-aligned or not), per-unit rotations, apply_lr pairs
 (v1c_remap_lut) on random float32 maps sprinkled with NaN, infinities, 2^15 / 2^26 / 2^31-scale values and ties of the 1/32 grid.
 
     python3 tools/fuzz.py [--seconds 300] [--seed 1] [--big 0.15] [--lut 0.15] [--hot 0.3] [--gen2 0] [--api 0.1] [--auto 0.06] [--fused 0.06] [--log gpurun_out/fuzz.log]
+                          [--wide 0] [--png 0]
+
+--wide P: that share of the cases has uint16 or float32 pixels (k_remap_wide): the chain cases above -- same grammar, views, batches, pairs,
+per-unit rotations, graph replays and the same three masks, counted in the same counters -- and the LUT cases (v1c_remap_lut_ex, nothing left
+out), against tests/wide_ref.py's restatement of cv2's float-weight remap on the oracle's map; a third of the float32 sources hold denormals,
+values next to FLT_MAX, signed zeros, infinities and NaN.  Outputs stay under 640 px (320 px for the 4 x 4 and 8 x 8 kernels) so that the NumPy
+restatement takes seconds.  A wide chain case whose masks leave out more than 5 % of its pixels is checked like any other but does not count
+towards the run's case total (the summary line says how many).  --png P: that share goes through the device PNG encoder
+(encode_png_tensor) -- a remap result as it lies on the device, or a synthetic image of tests/png_cases.py's generators (run planes across the
+kernels' 64-lane steps, 256-byte segments and 64-segment groups, noise, Fibonacci frequencies; gray / BGR / BGRA, 8- and 16-bit) in a random
+view with a random band height and either filter -- against tests/png_ref.py's file, byte for byte.  Both shares come off the top of the case
+draw: with both at 0 every earlier seed replays as it ran.
 
 Round 5 added to the grammar: hot shapes of the chains that left the interpreter (planar fisheye -> fisheye, is_latitude_y=False, a
 rotation behind radial stages), outputs of 64 ... 416 px, launches recorded into a graph and replayed, radius='auto' with the radius on
@@ -42,6 +54,7 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
 import chainspecs as CS  # noqa: E402
+import wide_ref as W  # noqa: E402
 import vr180_convert_amd as V  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 
@@ -104,6 +117,29 @@ def rand_size(rng, big: float, lo: int = 1):
     return int(rng.integers(lo, 300))
 
 
+WIDE_BVS = [70000, -3, 2.5, 1.5, 0.25, (70000, -3, 2.5), (1.5, 0.25, -3, 2.5), (1e-40, 3e38, -1, 2), 0, 300, (12, 40000, 7.5, 65535)]
+EXTREME_PIXELS = np.array([1e-45, -1e-45, 1e-39, 1.1754943508222875e-38, 3.4e38, -3.4e38, 0.0, -0.0, np.inf, -np.inf, np.nan], np.float32)
+
+
+def rand_pixels(rng, shape, dtype, extremes: bool = False) -> np.ndarray:
+    """random pixels of a wide type: uint16 full scale; float32 around 120 with negatives, now and then (`extremes`) sprinkled with
+    denormals, values next to FLT_MAX, signed zeros, infinities and NaN"""
+    if dtype == np.uint16:
+        return rng.integers(0, 65536, shape).astype(np.uint16)
+    a = rng.normal(120.0, 90.0, shape).astype(np.float32)
+    if extremes:
+        m = rng.random(shape) < 0.05
+        a[m] = rng.choice(EXTREME_PIXELS, int(m.sum()))
+    return a
+
+
+def neq(got: np.ndarray, want: np.ndarray) -> np.ndarray:
+    """elementwise "differs": bytes for the integer types; float32: equal, with NaN <=> NaN"""
+    if got.dtype != np.float32:
+        return got != want
+    return ~((got == want) | (np.isnan(got) & np.isnan(want)))
+
+
 def make_view(rng, arr: np.ndarray, dev, allow_unaligned: bool):
     """the array as a device tensor: contiguous, or a column slice of a wider buffer (pitched; offset dword-aligned or not)"""
     h, w, cn = arr.shape
@@ -111,7 +147,10 @@ def make_view(rng, arr: np.ndarray, dev, allow_unaligned: bool):
         return torch.from_numpy(arr).to(dev)
     pad_l = int(rng.integers(0, 9)) if allow_unaligned and rng.random() < 0.3 else 4 * int(rng.integers(0, 5))
     pad_r = int(rng.integers(0, 9)) if allow_unaligned and rng.random() < 0.3 else 4 * int(rng.integers(0, 5))
-    wide = rng.integers(0, 256, (h, pad_l + w + pad_r, cn), dtype=np.uint8)
+    if arr.dtype == np.uint8:
+        wide = rng.integers(0, 256, (h, pad_l + w + pad_r, cn), dtype=np.uint8)
+    else:  # (pads in pixels: an odd one leaves a uint16 view of cn 1 / 3 2-byte aligned only)
+        wide = rand_pixels(rng, (h, pad_l + w + pad_r, cn), arr.dtype.type)
     wide[:, pad_l:pad_l + w] = arr
     return torch.from_numpy(wide).to(dev)[:, pad_l:pad_l + w]
 
@@ -122,11 +161,13 @@ GEN2 = [0.0]  # share of the chain cases forced into general mode 2 (--gen2)
 KINDS: dict = {}  # kernel family -> launch groups it served (remapper.last_launch_kinds): which kernels the run reached
 SINGULAR = [0]  # differing pixels among the ill-conditioned ones that are left out (module docstring)
 TIES = [0]  # ... among those at a float32 rounding tie (float32_ties)
+LAST_MASKED = [0.0]  # share of the last chain case's pixels that its masks left out (the largest over its units)
+WIDE_CHAIN = {"run": 0, "not counted": 0, "masked px": 0, "px": 0}  # chain cases of --wide: a case with more than 5 % masked is not counted
 
 
 def dump_diff(k, got, want, maps, pmaps=None, fill=None) -> None:
     """where unit k differs: counts, bounding box, the first pixels with their map coordinates (the oracle's and the product's)"""
-    d = np.argwhere((got != want).any(axis=2))
+    d = np.argwhere(neq(got, want).any(axis=2))
     print(f"  unit {k}: {len(d)} pixels differ, rows {d[:, 0].min()}..{d[:, 0].max()}, cols {d[:, 1].min()}..{d[:, 1].max()}; "
           f"rows mod 16 {sorted(set((d[:, 0] % 16).tolist()))[:16]}, cols//4 mod 16 {sorted(set(((d[:, 1] // 4) % 16).tolist()))[:16]}")
     for (j, i) in d[:12]:
@@ -167,8 +208,12 @@ def float32_ties(spec, radius, size_in, size_out) -> np.ndarray:
             tie |= np.minimum(np.abs(v - m1), np.abs(v - m2)) <= 1e-14 * np.abs(v)
     return tie
 
-def one_case(rng, dev, big: float) -> tuple[str, int]:
-    """runs one random case; returns (description, number of differing bytes)"""
+def one_case(rng, dev, big: float, dtype=np.uint8) -> tuple[str, int]:
+    """runs one random case; returns (description, number of differing bytes).  `dtype` uint16 / float32 (--wide): the same chains, views,
+    batches, pairs and masks with 16-bit or float32 pixels, against wide_ref.remap on the oracle's map, at sizes that keep the NumPy
+    restatement in seconds"""
+    wide = dtype != np.uint8
+    LAST_MASKED[0] = 0.0
     spec, rot_at = rand_spec(rng)
     cn = int(rng.choice([3, 3, 3, 1, 4]))
     interp = int(rng.choice([1, 1, 1, 0, 2, 4, 4]))
@@ -275,6 +320,12 @@ def one_case(rng, dev, big: float) -> tuple[str, int]:
         pair = rng.random() < 0.4
         n = 2 if pair else int(rng.choice([1, 1, 2, 3]))
         unaligned_views = rng.random() < 0.15
+    if wide:
+        cap = 320 if interp in (2, 4) else 640
+        wo, ho, ws, hs = min(wo, cap), min(ho, cap), min(ws, 1000), min(hs, 1000)
+        if not pair and wo * ho * n > 3e5:
+            n = max(1, int(3e5 // (wo * ho)))
+        bval = WIDE_BVS[int(rng.integers(len(WIDE_BVS)))]
     rots = [rand_rot(rng, False) for _ in range(n)] if use_rot else None
     # units of different source sizes behind one transformer: the map is for images[0] (remapper.py:385), every image is
     # sampled within its own bounds; a pair of per-eye transformers (remapper.py:460-473): every eye its own chain and geometry
@@ -284,13 +335,17 @@ def one_case(rng, dev, big: float) -> tuple[str, int]:
     if mixed or (tuple_t and rng.random() < 0.5):
         sizes = [(hs, ws)] + [(max(1, hs + int(rng.integers(-40, 41))), max(1, ws + int(rng.integers(-40, 41)))) for _ in range(n - 1)]
     spec2 = rand_spec(rng)[0] if tuple_t else None
-    imgs = [rng.integers(0, 256, (h_, w_, cn), dtype=np.uint8) for (h_, w_) in sizes]
+    if wide:
+        ext = rng.random() < 0.33
+        imgs = [rand_pixels(rng, (h_, w_, cn), dtype, ext) for (h_, w_) in sizes]
+    else:
+        imgs = [rng.integers(0, 256, (h_, w_, cn), dtype=np.uint8) for (h_, w_) in sizes]
     if rng.random() < 0.3:  # a fisheye disc with a black surround, like the real inputs
         for im in imgs:
             yy, xx = np.mgrid[:im.shape[0], :im.shape[1]]
             im[((xx - im.shape[1] // 2) ** 2 + (yy - im.shape[0] // 2) ** 2) > (min(im.shape[:2]) / 2) ** 2] = 0
-    fill = rng.integers(0, 256, (ho, wo, cn), dtype=np.uint8)
-    desc = (f"spec={spec!r} cn={cn} interp={interp} border={border} bval={bval!r} out=({wo},{ho}) src=({ws},{hs}) radius={radius!r} n={n} pair={pair} "
+    fill = rand_pixels(rng, (ho, wo, cn), dtype) if wide else rng.integers(0, 256, (ho, wo, cn), dtype=np.uint8)
+    desc = (f"{np.dtype(dtype).name} " if wide else "") + (f"spec={spec!r} cn={cn} interp={interp} border={border} bval={bval!r} out=({wo},{ho}) src=({ws},{hs}) radius={radius!r} n={n} pair={pair} "
             f"rots={use_rot}" + (f" sizes={sizes!r}" if sizes[1:] != sizes[:-1] else "") + (f" right_eye_spec={spec2!r}" if tuple_t else ""))
     t = CS.to_product(spec)
     srcs = [make_view(rng, im, dev, allow_unaligned=unaligned_views) for im in imgs]
@@ -342,25 +397,30 @@ def one_case(rng, dev, big: float) -> tuple[str, int]:
             sing = None
         elif maps is None:
             maps = O.get_map(spec, radius=radius, size_input=(hs, ws), size_output=(wo, ho))
-        want = O.remap(imgs[k], maps[0], maps[1], interp, border, bval, dst=fill.copy())
+        want = (W.remap if wide else O.remap)(imgs[k], maps[0], maps[1], interp, border, bval, dst=fill.copy())
         if use_rot or tuple_t or sing is None:
             sp_now = sp if use_rot else (spec2 if (tuple_t and k == 1) else spec)
             sing = ill_conditioned(sp_now, radius, sizes[k] if tuple_t else (hs, ws), (wo, ho))
             if border in (1, 2, 3, 4):
                 sing |= ~((np.abs(maps[0]) < 2.0 ** 20) & (np.abs(maps[1]) < 2.0 ** 20))  # (NaN counts as singular)
         if sing is not None and sing.any():
-            diff = (got[k] != want).any(axis=2)
+            diff = neq(got[k], want).any(axis=2)
             SINGULAR[0] += int((diff & sing).sum())
             want = want.copy()
             want[sing] = got[k][sing]
-        if (got[k] != want).any() and not use_rot:
+            LAST_MASKED[0] = max(LAST_MASKED[0], float(sing.mean()))
+            if wide:
+                WIDE_CHAIN["masked px"] += int(sing.sum())
+        if wide:
+            WIDE_CHAIN["px"] += wo * ho
+        if neq(got[k], want).any() and not use_rot:
             tie = float32_ties(spec2 if (tuple_t and k == 1) else spec, radius, sizes[k] if tuple_t else (hs, ws), (wo, ho))
             if tie.any():
-                TIES[0] += int(((got[k] != want).any(axis=2) & tie).sum())
+                TIES[0] += int((neq(got[k], want).any(axis=2) & tie).sum())
                 want = want.copy()
                 want[tie] = got[k][tie]
-        bad += int((got[k] != want).sum())
-        if DUMP[0] and (got[k] != want).any():
+        bad += int(neq(got[k], want).sum())
+        if DUMP[0] and neq(got[k], want).any():
             pm = None
             try:
                 sp_k = (spec2 if (tuple_t and k == 1) else spec) if not use_rot else sp
@@ -371,9 +431,11 @@ def one_case(rng, dev, big: float) -> tuple[str, int]:
     return desc, bad
 
 
-def lut_case(rng, dev) -> tuple[str, int]:
+def lut_case(rng, dev, dtype=np.uint8) -> tuple[str, int]:
     """cv2.remap alone (v1c_remap_lut, what chains with user-defined stages use) on random float32 maps: smooth, noisy, and
-    sprinkled with the values the fixed-point conversion treats specially"""
+    sprinkled with the values the fixed-point conversion treats specially.  `dtype` uint16 / float32 (--wide): v1c_remap_lut_ex
+    against wide_ref.remap, nothing left out"""
+    wide = dtype != np.uint8
     import ctypes as C
 
     from vr180_convert_amd import _native
@@ -385,7 +447,13 @@ def lut_case(rng, dev) -> tuple[str, int]:
     bval = tuple(int(x) for x in rng.integers(0, 256, int(rng.integers(1, 5))))
     hs, ws = int(rng.integers(1, 400)), int(rng.integers(1, 400))
     ho, wo = int(rng.integers(1, 500)), int(rng.integers(1, 500))
-    src = rng.integers(0, 256, (hs, ws, cn), dtype=np.uint8)
+    if wide:
+        if interp in (2, 4):
+            ho, wo = min(ho, 300), min(wo, 300)
+        bval = WIDE_BVS[int(rng.integers(len(WIDE_BVS)))]
+        src = rand_pixels(rng, (hs, ws, cn), dtype, rng.random() < 0.33)
+    else:
+        src = rng.integers(0, 256, (hs, ws, cn), dtype=np.uint8)
     jj, ii = np.mgrid[:ho, :wo].astype(np.float64)
     kind = int(rng.integers(0, 3))
     if kind == 0:  # affine + noise
@@ -408,18 +476,28 @@ def lut_case(rng, dev) -> tuple[str, int]:
     xw = np.zeros((ho, wo + pad), np.float32)
     yw = np.zeros((ho, wo + pad), np.float32)
     xw[:, :wo], yw[:, :wo] = xm, ym
-    fill = rng.integers(0, 256, (ho, wo, cn), dtype=np.uint8)
+    fill = rand_pixels(rng, (ho, wo, cn), dtype) if wide else rng.integers(0, 256, (ho, wo, cn), dtype=np.uint8)
     s_d = make_view(rng, src, dev, allow_unaligned=True)
     d_d = make_view(rng, fill.copy(), dev, allow_unaligned=True)
     x_d, y_d = torch.from_numpy(xw).to(dev), torch.from_numpy(yw).to(dev)
-    bv = border_scalar(bval)
-    rc = _native.lib().v1c_remap_lut(dev.index, _stream_ptr(dev), s_d.data_ptr(), hs, ws, s_d.stride(0), cn, d_d.data_ptr(), ho, wo, d_d.stride(0),
-                                     x_d.data_ptr(), y_d.data_ptr(), x_d.stride(0) * 4, interp, border, bv.ctypes.data)
-    _native.check(rc, "v1c_remap_lut")
+    if wide:
+        from vr180_convert_amd.remapper import DEPTHS, border_scalar_f64
+
+        bv, es = border_scalar_f64(bval), src.dtype.itemsize
+        rc = _native.lib().v1c_remap_lut_ex(dev.index, _stream_ptr(dev), s_d.data_ptr(), hs, ws, (s_d.stride(0) if hs > 1 else ws * cn) * es, cn,
+                                            DEPTHS[s_d.dtype], d_d.data_ptr(), ho, wo, (d_d.stride(0) if ho > 1 else wo * cn) * es, x_d.data_ptr(),
+                                            y_d.data_ptr(), x_d.stride(0) * 4, interp, border, bv.ctypes.data)
+        _native.check(rc, "v1c_remap_lut_ex")
+        KINDS["lut_ex"] = KINDS.get("lut_ex", 0) + 1
+    else:
+        bv = border_scalar(bval)
+        rc = _native.lib().v1c_remap_lut(dev.index, _stream_ptr(dev), s_d.data_ptr(), hs, ws, s_d.stride(0), cn, d_d.data_ptr(), ho, wo, d_d.stride(0),
+                                         x_d.data_ptr(), y_d.data_ptr(), x_d.stride(0) * 4, interp, border, bv.ctypes.data)
+        _native.check(rc, "v1c_remap_lut")
     got = d_d.cpu().numpy()
-    want = O.remap(src, xm, ym, interp, border, bval, dst=fill.copy())
-    bad = int((got != want).sum())
-    desc = f"LUT cn={cn} interp={interp} border={border} bval={bval!r} out=({wo},{ho}) src=({ws},{hs}) maps={kind} map_pad={pad}"
+    want = (W.remap if wide else O.remap)(src, xm, ym, interp, border, bval, dst=fill.copy())
+    bad = int(neq(got, want).sum())
+    desc = (f"{np.dtype(dtype).name} " if wide else "") + f"LUT cn={cn} interp={interp} border={border} bval={bval!r} out=({wo},{ho}) src=({ws},{hs}) maps={kind} map_pad={pad}"
     if bad and DUMP[0]:
         dump_diff(0, got, want, (xm, ym))
     return desc, bad
@@ -647,6 +725,47 @@ def radius_case(rng, dev) -> tuple[str, int]:
     return f"RADIUS cn={cn} size=({w},{h}) threshold={thr} want={want} got={got}", 0 if got == want else 1
 
 
+def png_case(rng, dev) -> tuple[str, int]:
+    """the device PNG encoder (encode_png_tensor) against its NumPy restatement (png_ref.encode), the file byte for byte: a remap result
+    as it lies on the device (one eye's half of a side-by-side tensor now and then), or a synthetic image of tests/png_cases.py's
+    generators -- run planes, noise, Fibonacci frequencies, noise above runs; gray / BGR / BGRA, 8- and 16-bit -- with random
+    parameters, in a random view; either filter, a random band height"""
+    import png_cases as PC
+    import png_ref as PR
+
+    filt = "up" if rng.random() < 0.5 else "paeth"
+    if rng.random() < 0.35:
+        spec, _ = rand_spec(rng)
+        dtype = np.uint8 if rng.random() < 0.7 else np.uint16
+        cn = int(rng.choice([3, 3, 1, 4]))
+        wo, ho, hs, ws = (int(v) for v in rng.integers(1, 600, 4))
+        src = rng.integers(0, 256, (hs, ws, cn), dtype=np.uint8) if dtype == np.uint8 else rand_pixels(rng, (hs, ws, cn), dtype)
+        radius = float(rng.uniform(0.3, 1.2) * min(ws, hs) / 2 + 1.0)
+        s_d = torch.from_numpy(src).to(dev)
+        if rng.random() < 0.5:
+            sbs = V.apply_lr_tensors(CS.to_product(spec), s_d, s_d, size_output=(wo, ho), interpolation=int(rng.choice([0, 1, 4])), radius=radius)
+            t = sbs[:, wo:] if rng.random() < 0.5 else sbs
+        else:
+            t = torch.zeros((ho, wo, cn), dtype=s_d.dtype, device=dev)
+            V.remap_tensors(CS.to_product(spec), [s_d], [t], radius=radius, interpolation=int(rng.choice([0, 1, 4])))
+        img = np.ascontiguousarray(t.cpu().numpy())
+        rows = None if rng.random() < 0.3 else int(rng.integers(1, ho + 1))
+        desc = f"remap result {np.dtype(dtype).name} {tuple(img.shape)} contiguous={t.is_contiguous()} spec={spec!r} src=({ws},{hs}) radius={radius!r}"
+    else:
+        desc, img, rows = PC.random_image(rng)
+        t = make_view(rng, img, dev, allow_unaligned=True)
+        desc += f" contiguous={t.is_contiguous()} byte offset={t.storage_offset() * img.dtype.itemsize}"
+    from vr180_convert_amd import png_device
+
+    h, w, cn = img.shape
+    rows_used = png_device.default_band_rows(h, 1 + w * cn * img.dtype.itemsize) if rows is None else rows
+    got = V.encode_png_tensor(t, filter=filt, band_rows=rows)
+    want = PR.encode(img, filter=filt, band_rows=rows_used)
+    KINDS["png"] = KINDS.get("png", 0) + 1
+    bad = abs(len(got) - len(want)) + sum(a != b for a, b in zip(got, want)) if got != want else 0
+    return f"PNG filter={filt} band_rows={rows!r} {desc}", bad
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=300)
@@ -658,6 +777,8 @@ def main() -> int:
     ap.add_argument("--api", type=float, default=0.1, help="share of cases through apply() / apply_lr() on host arrays")
     ap.add_argument("--auto", type=float, default=0.06, help="share of cases through apply_lr_tensors(radius='auto') with the radius on the device")
     ap.add_argument("--fused", type=float, default=0.06, help="share of cases through v1c_remap_fused by raw ctypes")
+    ap.add_argument("--wide", type=float, default=0.0, help="share of cases with uint16 / float32 pixels: the chain cases and the LUT cases (k_remap_wide) against wide_ref.remap")
+    ap.add_argument("--png", type=float, default=0.0, help="share of cases through the device PNG encoder (encode_png_tensor) against png_ref.encode")
     ap.add_argument("--only", type=int, default=None, help="run only this case number (reproduce)")
     ap.add_argument("--log", default=None)
     ap.add_argument("--trace", default=None, help="file that always holds the number of the case being run")
@@ -688,7 +809,17 @@ def main() -> int:
                 tf.write(f"seed {a.seed} case {a.only if a.only is not None else case}\n")
         try:
             r_kind = rng.random()
-            if r_kind < a.lut:
+            wide_chain = False
+            if r_kind >= 1.0 - a.png:  # (the new shares come off the top: with both at 0 every earlier seed replays as it ran)
+                desc, bad = png_case(rng, dev)
+            elif r_kind >= 1.0 - a.png - a.wide:
+                dtype = np.uint16 if rng.random() < 0.5 else np.float32
+                if rng.random() < 0.3:
+                    desc, bad = lut_case(rng, dev, dtype)
+                else:
+                    wide_chain = True
+                    desc, bad = one_case(rng, dev, a.big, dtype)
+            elif r_kind < a.lut:
                 desc, bad = lut_case(rng, dev)
             elif r_kind < a.lut + 0.05:
                 desc, bad = radius_case(rng, dev)
@@ -703,6 +834,11 @@ def main() -> int:
         except Exception as e:  # noqa: BLE001 -- a refusal of the product (documented limits) is reported, not fatal
             desc, bad = f"EXCEPTION {type(e).__name__}: {e}", -1
         n_cases += 1
+        if wide_chain and bad >= 0:
+            WIDE_CHAIN["run"] += 1
+            if LAST_MASKED[0] > 0.05:  # mostly masks, little comparison: checked like every case, but not a case of the run's total
+                WIDE_CHAIN["not counted"] += 1
+                n_cases -= 1
         if bad != 0:
             n_bad += 1
             say(f"[case {a.only if a.only is not None else case}] {'MISMATCH ' + str(bad) + ' bytes' if bad > 0 else ''} {desc}")
@@ -714,7 +850,9 @@ def main() -> int:
             last = time.time()
             say(f"... {n_cases} cases, {n_bad} reported, {time.time() - t0:.0f} s")
     say(f"fuzz seed {a.seed}: {n_cases} cases in {time.time() - t0:.0f} s, {n_bad} reported; {SINGULAR[0]} differing ill-conditioned pixels left out"
-        + (f", {TIES[0]} at float32 rounding ties" if TIES[0] else ""))
+        + (f", {TIES[0]} at float32 rounding ties" if TIES[0] else "")
+        + (f"; wide chain cases: {WIDE_CHAIN['run']} run, {WIDE_CHAIN['not counted']} of them over 5 % masked and not counted, "
+           f"{WIDE_CHAIN['masked px']} of {WIDE_CHAIN['px']} pixels masked" if WIDE_CHAIN["run"] else ""))
     say("kernel families of the chain cases' launch groups: " + ", ".join(f"{k} x{v}" for k, v in sorted(KINDS.items())))
     return 1 if n_bad else 0
 
