@@ -320,7 +320,8 @@ int v1c_build_ftab(int interp, float* out);
 /* ---- feature matching of the two eyes (--automatch devfm; replaces the cv2.AKAZE + BFMatcher front end of remapper.py:194-248) --
  * NOT AKAZE: a single-scale, oriented binary-feature pipeline whose every stage is integer arithmetic, so that its keypoints,
  * descriptors and matches are reproducible bit for bit (INTEGRATION.md section 5 states the contract; tests/feat_ref.py restates it).
- * Defaults in brackets.                                                                                                          */
+ * Defaults in brackets.  `radius` must be positive: get_radius_smart("auto") is negative on an image circle on black (the reference's
+ * sign quirk: the 180-degree flip of a map); the qualifying disc is symmetric, and the Python layer passes |radius|.               */
 typedef struct v1c_feat_params {
     double  scale;          /* working scale s in (0, 1]: working size (int(w * s), int(h * s)), block-mean resampling [1]      */
     double  radius;         /* image-circle radius in ORIGINAL pixels (what get_radius_smart resolves), centre (w / 2, h / 2)   */

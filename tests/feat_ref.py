@@ -256,3 +256,74 @@ def match(desc1: np.ndarray, desc2: np.ndarray, max_distance: int = 64, ratio: t
     i = np.arange(len(d))
     keep = (i21[i12] == i) & (d1 <= max_distance) & (den * d1 <= num * d2)
     return i[keep], i12[keep], d1[keep]
+
+
+# ---- stage 6 for large sets: the same rule, the distances a block of rows at a time --------------------------------------------------
+BLOCK_BYTES = 64 << 20  # the int32 distances held at a time (`distances` of 17000 x 9000 descriptors would take ~2 GB with its temporaries)
+
+
+def _two_smallest(d: np.ndarray, axis: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """along `axis`: smallest value, its lowest index, second-smallest value (NO_SECOND with one entry); `d` comes back unchanged"""
+    idx = d.argmin(axis)
+    at = (np.arange(d.shape[0]), idx) if axis == 1 else (idx, np.arange(d.shape[1]))
+    d1 = d[at]
+    if d.shape[axis] == 1:
+        return d1, idx, np.full(len(d1), NO_SECOND, np.int64)
+    d[at] = NO_SECOND
+    d2 = d.min(axis)
+    d[at] = d1
+    return d1, idx, d2.astype(np.int64)
+
+
+def best_both(desc1: np.ndarray, desc2: np.ndarray, block_bytes: int = BLOCK_BYTES):
+    """((d1, idx, d2) of every row, (d1, idx, d2) of every column) of the distance matrix, which is never held whole: blocks of rows of
+    at most `block_bytes`, the rows' results block by block and a running best / lowest index / second best of every column.  Both sets
+    non-empty."""
+    na, nb = len(desc1), len(desc2)
+    step = max(1, block_bytes // (4 * nb))
+    rows = [np.zeros(na, np.int64) for _ in range(3)]
+    c1, ci, c2 = np.full(nb, NO_SECOND, np.int64), np.full(nb, -1, np.int64), np.full(nb, NO_SECOND, np.int64)
+    for r0 in range(0, na, step):
+        d = distances(desc1[r0:r0 + step], desc2)
+        for out, v in zip(rows, _two_smallest(d, 1)):
+            out[r0:r0 + step] = v
+        b1, bi, b2 = _two_smallest(d, 0)
+        # this block's rows come after every earlier one: only a strictly smaller distance takes the column over
+        take = b1 < c1
+        c2 = np.where(take, np.minimum(c1, b2), np.minimum(b1, c2))
+        ci = np.where(take, bi + r0, ci)
+        c1 = np.where(take, b1, c1)
+    return tuple(rows), (c1, ci, c2)
+
+
+def match_from_best(rows, cols, max_distance: int = 64, ratio: tuple[int, int] = (3, 4)):
+    """the match rule on `best_both`'s results (swap them for the other argument order)"""
+    d1, i12, d2 = rows
+    num, den = ratio
+    i = np.arange(len(d1))
+    keep = (cols[1][i12] == i) & (d1 <= max_distance) & (den * d1 <= num * d2)
+    return i[keep], i12[keep], d1[keep]
+
+
+def match_blocked(desc1: np.ndarray, desc2: np.ndarray, max_distance: int = 64, ratio: tuple[int, int] = (3, 4),
+                  block_bytes: int = BLOCK_BYTES):
+    """`match`, with at most `block_bytes` of distances in memory"""
+    if len(desc1) == 0 or len(desc2) == 0:
+        e = np.zeros(0, np.int64)
+        return e, e, e
+    return match_from_best(*best_both(desc1, desc2, block_bytes), max_distance, ratio)
+
+
+# ---- what v1c_feat_detect refuses -----------------------------------------------------------------------------------------------------
+def refusal(h: int, w: int, scale: float, radius: float, margin: int) -> str | None:
+    """why v1c_feat_detect answers V1C_E_INVALID for an (h, w) image with in-range parameters, or None where it runs: a working image
+    under 33 x 33, an empty source block, or no qualifying pixel"""
+    ww, wh = working_size(h, w, scale)
+    if ww < 2 * BORDER + 1 or wh < 2 * BORDER + 1:
+        return "working image under 33 x 33"
+    if (np.diff(bounds(wh, h, scale)) <= 0).any() or (np.diff(bounds(ww, w, scale)) <= 0).any():
+        return "empty source block"
+    rg = disc_ranges(h, w, scale, radius, margin)
+    if not (rg[:, 0] <= rg[:, 1]).any():
+        return "empty circle"
+    return None

@@ -94,6 +94,107 @@ def test_restated_matcher_equals_plain_brute_force():
     assert (3, 10) in zip(i1.tolist(), i2.tolist()) and (5, 30) in zip(i1.tolist(), i2.tolist()) and (40, 7) in zip(i1.tolist(), i2.tolist())
 
 
+def _tied_sets(seed, na, nb):
+    """random descriptors with near copies, exact duplicates on both sides and tied non-zero distances"""
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, 256, (na, 32), dtype=np.uint8)
+    b = rng.integers(0, 256, (nb, 32), dtype=np.uint8)
+    if nb > 40:
+        k = na // 3
+        a[:k] = b[rng.integers(0, nb, k)] ^ rng.integers(0, 2, (k, 32), dtype=np.uint8)
+        b[10] = b[20] = b[nb - 1] = a[na - 1]       # three candidates at distance 0 of one query, the last index among them
+        b[30] = b[31] = a[na - 2] ^ 1               # a tied non-zero best
+        if na > 40:
+            a[5] = a[6] = a[na // 2] = b[3]         # ... and duplicates among the queries: ties of the columns
+    return a, b
+
+
+@pytest.mark.parametrize("na,nb", [(300, 211), (211, 300), (257, 1), (1, 257), (64, 64)])
+def test_blocked_matcher_equals_the_unblocked_one(na, nb):
+    """feat_ref.match_blocked (rows a block at a time, a running best / lowest index / second best of every column) against
+    feat_ref.match on one matrix: blocks of 1, 7 and 100 rows and a single block, nb == 1 (NO_SECOND), exact duplicates, every ratio and
+    max_distance the GPU fuzz draws; and the column results, which serve the swapped argument order"""
+    a, b = _tied_sets(na * 1000 + nb, na, nb)
+    d = R.distances(a, b)
+    for rows in (1, 7, 100, na):
+        got_rows, got_cols = R.best_both(a, b, block_bytes=rows * 4 * nb)
+        assert all(np.array_equal(g, w) for g, w in zip(got_rows, R.best(d))), rows
+        assert all(np.array_equal(g, w) for g, w in zip(got_cols, R.best(d.T))), rows
+    assert np.array_equal(d, R.distances(a, b))
+    if nb == 1:
+        assert (got_rows[2] == R.NO_SECOND).all()
+    n_kept = 0
+    for dmax in (0, 16, 64, 256):
+        for ratio in ((3, 4), (1, 1), (1, 2), (0, 1)):
+            want = R.match(a, b, max_distance=dmax, ratio=ratio)
+            got = R.match_blocked(a, b, max_distance=dmax, ratio=ratio, block_bytes=7 * 4 * nb)
+            assert all(np.array_equal(g, w) for g, w in zip(got, want)), (dmax, ratio)
+            back = R.match_from_best(got_cols, got_rows, dmax, ratio)
+            assert all(np.array_equal(g, w) for g, w in zip(back, R.match(b, a, max_distance=dmax, ratio=ratio))), (dmax, ratio)
+            n_kept += len(want[0])
+    assert n_kept > 0
+    for x, y in ((a[:0], b), (a, b[:0])):
+        assert all(len(v) == 0 for v in R.match_blocked(x, y))
+
+
+def test_radius_helper_hands_the_magnitude_of_the_auto_radius_to_the_detector(product_lib):
+    """radius="auto" on an image circle on black is negative (the reference's sign quirk, kept); v1c_feat_detect refuses radius <= 0, so
+    features.resolve_radius gives its magnitude -- for one image and for a pair -- and leaves "max" and numbers alone."""
+    from vr180_convert_amd import features as F
+    from vr180_convert_amd.chain import get_radius
+    from vr180_convert_amd.remapper import get_radius_smart
+
+    rng = np.random.default_rng(1)
+    yy, xx = np.mgrid[:480, :640]
+    disc = rng.integers(30, 256, (480, 640, 3), dtype=np.uint8)
+    disc[(xx - 320) ** 2 + (yy - 240) ** 2 > 200 ** 2] = 0
+    yy, xx = np.mgrid[:512, :512]
+    disc2 = rng.integers(30, 256, (512, 512, 3), dtype=np.uint8)
+    disc2[(xx - 256) ** 2 + (yy - 256) ** 2 > 230 ** 2] = 0
+    assert get_radius(disc) == -200.5 and get_radius(disc2) == -230.5
+    assert F.resolve_radius("auto", [disc]) == 200.5 == -get_radius(disc)
+    assert F.resolve_radius("auto", [disc, disc2]) == abs(get_radius_smart("auto", [disc, disc2])) == 200.5
+    assert F.resolve_radius("max", [disc]) == 240.0 and F.resolve_radius(123.25, [disc]) == 123.25
+    assert F.params(1.0, F.resolve_radius("auto", [disc])).radius > 0
+    # what the detector answered to the raw value (before any device call): the refusal that `lr --automatch devfm` ended in
+    buf, prm = np.zeros(1 << 16, np.uint8), F.params(1.0, get_radius_smart("auto", [disc]))
+    assert product_lib.v1c_feat_detect(0, None, _ptr(buf), 480, 640, 640 * 3, 3, C.byref(prm), _ptr(buf), _ptr(buf), _ptr(buf)) == -1
+    assert "radius must lie in (0, 1e9]" in product_lib.v1c_last_error().decode()
+    with pytest.raises(IndexError):  # no black border: what the reference's match_lr raises too
+        F.resolve_radius("auto", [rng.integers(30, 256, (64, 64, 3), dtype=np.uint8)])
+
+
+def test_feat_fuzz_draws_few_cases_that_the_detector_refuses():
+    """tools/fuzz.py --feat draws sizes, scales, radii and margins so that v1c_feat_detect refuses a small minority (a working image under
+    33 x 33, an empty circle): feat_ref.refusal over 3000 draws of the seed the GPU suite runs stays under 8 % -- the GPU slice fails
+    above 10 % --, both reasons occur, and the predicate agrees with the library's own argument checks (which run before any device call)."""
+    import importlib.util
+
+    from vr180_convert_amd import _native
+    from vr180_convert_amd import features as F
+
+    sp = importlib.util.spec_from_file_location("v1c_fuzz_tool", ROOT / "tools" / "fuzz.py")
+    Z = importlib.util.module_from_spec(sp)
+    sp.loader.exec_module(Z)
+    lib = _native.lib()
+    buf = np.zeros(700 * 700 * 4 + 64, np.uint8)  # stands in for the device image: a refusal comes before any device call
+    why = {}
+    for case in range(3000):
+        rng = np.random.default_rng([203, case])
+        rng.random()
+        p = Z.feat_draw(rng)
+        r = R.refusal(p["h"], p["w"], p["scale"], p["radius"], p["margin"])
+        why[r] = why.get(r, 0) + 1
+        if r is not None:
+            prm = F.params(p["scale"], p["radius"], margin=p["margin"])
+            rc = lib.v1c_feat_detect(0, None, _ptr(buf), p["h"], p["w"], p["w"] * p["cn"], p["cn"], C.byref(prm), _ptr(buf), _ptr(buf), _ptr(buf))
+            assert rc == -1 and any(t in lib.v1c_last_error().decode() for t in ("smaller than the pattern", "empty circle", "empty source")), (p, r)
+    print(why)
+    refused = 3000 - why.get(None, 0)
+    assert 0 < refused <= 0.08 * 3000, why
+    assert why.get("working image under 33 x 33", 0) > 0 and why.get("empty circle", 0) > 0, why
+
+
 # ---- the product's arithmetic on the host -------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("cn,s", [(1, 1.0), (3, 0.5), (4, 0.37), (3, 0.25)])
 def test_host_harness_equals_restatement_per_pixel(feat_emul, cn, s):

@@ -7,7 +7,7 @@ and destination views (dword-aligned or not), per-unit rotations, apply_lr pairs
 (v1c_remap_lut) on random float32 maps sprinkled with NaN, infinities, 2^15 / 2^26 / 2^31-scale values and ties of the 1/32 grid.
 
     python3 tools/fuzz.py [--seconds 300] [--seed 1] [--big 0.15] [--lut 0.15] [--hot 0.3] [--gen2 0] [--api 0.1] [--auto 0.06] [--fused 0.06] [--log gpurun_out/fuzz.log]
-                          [--wide 0] [--png 0]
+                          [--wide 0] [--png 0] [--feat 0]
 
 --wide P: that share of the cases has uint16 or float32 pixels (k_remap_wide): the chain cases above -- same grammar, views, batches, pairs,
 per-unit rotations, graph replays and the same three masks, counted in the same counters -- and the LUT cases (v1c_remap_lut_ex, nothing left
@@ -17,8 +17,13 @@ restatement takes seconds.  A wide chain case whose masks leave out more than 5 
 towards the run's case total (the summary line says how many).  --png P: that share goes through the device PNG encoder
 (encode_png_tensor) -- a remap result as it lies on the device, or a synthetic image of tests/png_cases.py's generators (run planes across the
 kernels' 64-lane steps, 256-byte segments and 64-segment groups, noise, Fibonacci frequencies; gray / BGR / BGRA, 8- and 16-bit) in a random
-view with a random band height and either filter -- against tests/png_ref.py's file, byte for byte.  Both shares come off the top of the case
-draw: with both at 0 every earlier seed replays as it ran.
+view with a random band height and either filter -- against tests/png_ref.py's file, byte for byte.  --feat P: that share goes through the feature
+pipeline of --automatch devfm (features.detect / features.match) against tests/feat_ref.py, keypoints, descriptors and matches equal: images of
+six kinds (noise discs, noise, low contrast, polygons and blobs on a gradient, rendered sphere scenes, flat) of 40 ... 700 px in random views,
+scale, radius, margin, threshold, cell, per_cell and the cap drawn off their defaults, the matcher on the descriptors of two detects or on random
+sets of 0 ... 20000 descriptors with planted copies, duplicates and ties.  A case that v1c_feat_detect refuses (working image under 33 x 33, empty
+circle) where feat_ref.refusal predicts it is correct and not counted (the summary line says how many).  The three shares come off the top of the
+case draw: with all of them at 0 every earlier seed replays as it ran.
 
 Round 5 added to the grammar: hot shapes of the chains that left the interpreter (planar fisheye -> fisheye, is_latitude_y=False, a
 rotation behind radial stages), outputs of 64 ... 416 px, launches recorded into a graph and replayed, radius='auto' with the radius on
@@ -766,6 +771,155 @@ def png_case(rng, dev) -> tuple[str, int]:
     return f"PNG filter={filt} band_rows={rows!r} {desc}", bad
 
 
+FEAT = {"drawn": 0, "refused": 0}  # feat cases drawn / of them refused by v1c_feat_detect as feat_ref.refusal predicts (not counted)
+FEAT_IMAGES = ["disc", "noise", "low", "scene", "sphere", "flat"]
+FEAT_RATIOS = [(3, 4), (1, 1), (1, 2), (0, 1)]
+
+
+def feat_draw(rng) -> dict:
+    """the draws of feat_case's detect half that decide whether v1c_feat_detect refuses the case: no image, no device (tests/test_feat_host.py
+    runs feat_ref.refusal over thousands of them).  Nine in ten sizes are drawn so that the working image reaches 34 pixels, nine in ten
+    margins so that radius * scale - margin stays at 2 or more: the rest may be refused (a working image under 33 x 33, an empty circle)"""
+    kind = FEAT_IMAGES[int(rng.integers(len(FEAT_IMAGES)))]
+    scale = [1.0, 0.5, 1 / 3, float(rng.uniform(0.2, 1.0))][int(rng.integers(4))]
+    lo = max(40, int(np.ceil(34 / scale))) if rng.random() < 0.9 else 40
+    h, w = int(rng.integers(lo, 701)), int(rng.integers(lo, 701))
+    if kind == "sphere":  # (sphere_scene.render: square, and seconds above a few hundred pixels)
+        h = w = min(h, w, 320)
+    cn = int(rng.choice([1, 3, 4]))
+    radius = float(rng.uniform(0.2, 1.5) * min(h, w) / 2)
+    margin = int(rng.integers(0, 41))
+    if rng.random() < 0.9:
+        margin = min(margin, max(0, int(radius * scale) - 2))
+    return {"kind": kind, "h": h, "w": w, "cn": cn, "gray2d": bool(cn == 1 and rng.random() < 0.3), "scale": scale, "radius": radius,
+            "margin": margin, "fast_threshold": int(rng.choice([1, 5, 20, 60, 255], p=[0.2, 0.25, 0.3, 0.2, 0.05])),
+            "cell": int(rng.choice([8, 16, 32, 47, 64])), "per_cell": int(rng.integers(1, 5)),
+            "max_keypoints": int(rng.choice([1, 7, 100, 8192, 65536], p=[0.1, 0.1, 0.2, 0.35, 0.25]))}  # (mostly cases with keypoints to match)
+
+
+def feat_image(rng, kind: str, h: int, w: int, cn: int) -> np.ndarray:
+    """(h, w, cn) uint8: a noise disc on black, uniform noise, low-contrast noise (0..30), filled polygons, discs and blobs on a gradient
+    (flat regions: corners of repeated scores), a rendered sphere scene, or a flat image (no keypoint)"""
+    if kind == "disc":
+        from vr180_convert_amd.synth import noise_disc
+
+        return noise_disc(h, w, int(rng.integers(1000)), cn=cn)
+    if kind == "noise":
+        return rng.integers(0, 256, (h, w, cn), dtype=np.uint8)
+    if kind == "low":
+        return rng.integers(0, 31, (h, w, cn), dtype=np.uint8)
+    if kind == "flat":
+        return np.full((h, w, cn), int(rng.integers(0, 256)), np.uint8)
+    if kind == "sphere":
+        import sphere_scene as S
+
+        g = S.render(h, S.rotation(rng.normal(0, 1, 3), float(rng.uniform(0, 20))))[..., :1]
+        return np.ascontiguousarray(np.concatenate([g, g, g, rng.integers(0, 256, (h, w, 1), dtype=np.uint8)], axis=2)[..., :cn])
+    yy, xx = np.mgrid[:h, :w].astype(np.float64)
+    a = 60 + 80 * (xx * rng.uniform(0, 1) / w + yy * rng.uniform(0, 1) / h)
+    for _ in range(int(rng.integers(3, 40))):
+        if rng.random() < 0.7:  # a filled triangle: inside iff on one side of all three edges
+            px, py = rng.uniform(-0.1 * w, 1.1 * w, 3), rng.uniform(-0.1 * h, 1.1 * h, 3)
+            e = [(px[(k + 1) % 3] - px[k]) * (yy - py[k]) - (py[(k + 1) % 3] - py[k]) * (xx - px[k]) for k in range(3)]
+            m = ((e[0] >= 0) & (e[1] >= 0) & (e[2] >= 0)) | ((e[0] <= 0) & (e[1] <= 0) & (e[2] <= 0))
+            a[m] = float(rng.choice([0, 40, 40, 200, 200, 255]))
+        elif rng.random() < 0.5:  # a filled disc
+            a[(xx - rng.uniform(0, w)) ** 2 + (yy - rng.uniform(0, h)) ** 2 <= rng.uniform(2, 30) ** 2] = float(rng.integers(0, 256))
+        else:  # a Gaussian blob
+            a += rng.uniform(-120, 120) * np.exp(-((xx - rng.uniform(0, w)) ** 2 + (yy - rng.uniform(0, h)) ** 2) / (2 * rng.uniform(1.5, 12) ** 2))
+    g = np.clip(np.rint(a), 0, 255).astype(np.uint8)
+    return np.ascontiguousarray(np.repeat(g[..., None], cn, axis=2))
+
+
+def feat_sets(rng) -> tuple[np.ndarray, np.ndarray]:
+    """two random descriptor sets with near copies (matches), exact duplicates and ties planted; sizes on the matcher's tile of 256"""
+    def size():
+        return int(rng.choice([0, 1, 255, 256, 257])) if rng.random() < 0.4 else int(np.exp(rng.uniform(np.log(300), np.log(20000))))
+
+    na, nb = size(), size()
+    a = rng.integers(0, 256, (na, 32), dtype=np.uint8)
+    b = rng.integers(0, 256, (nb, 32), dtype=np.uint8)
+    if na and nb:
+        k = (min(na, nb) + 2) // 3
+        a[:k] = b[rng.integers(0, nb, k)] ^ rng.integers(0, 2, (k, 32), dtype=np.uint8)  # up to 32 bits off a candidate
+        for _ in range(int(rng.integers(0, 6))):  # exact duplicates among the candidates, a query equal to them / one bit off them
+            j1, j2, i = int(rng.integers(nb)), int(rng.integers(nb)), int(rng.integers(na))
+            b[j2] = b[j1]
+            a[i] = b[j1]
+            a[i, 0] ^= int(rng.integers(0, 2))
+        for _ in range(int(rng.integers(0, 4))):  # ... and among the queries
+            a[int(rng.integers(na))] = a[int(rng.integers(na))]
+    return a, b
+
+
+def _differing(got, want) -> int:
+    """differing elements of two tuples of arrays; an array of another shape counts whole"""
+    return sum(int((np.asarray(g) != np.asarray(w)).sum()) if np.shape(g) == np.shape(w) else max(np.size(g), np.size(w), 1)
+               for g, w in zip(got, want))
+
+
+def feat_case(rng, dev) -> tuple[str, int, bool]:
+    """the feature pipeline (v1c_feat_detect / v1c_feat_match through features.detect / features.match) against tests/feat_ref.py, every
+    array equal, shapes included: images of six kinds in a random view with random parameters off the defaults; the matcher on the
+    descriptors of two such detects (the second image: the first one rolled a few pixels under a little noise, or an independent one), or,
+    a third of the time, on random descriptor sets of 0 ... 20000 entries with planted copies, duplicates and ties.  Returns (description,
+    differing elements, counted): a refusal of the product that feat_ref.refusal predicts is correct and does not count as a case."""
+    import feat_ref as R
+    from vr180_convert_amd import features as F
+
+    p = feat_draw(rng)
+    kind, h, w, cn = p["kind"], p["h"], p["w"], p["cn"]
+    kw = {k: p[k] for k in ("margin", "fast_threshold", "cell", "per_cell", "max_keypoints")}
+    img = feat_image(rng, kind, h, w, cn)
+    sets = rng.random() < 0.33
+    mkw = {"max_distance": int(rng.choice([0, 16, 64, 256])), "ratio": FEAT_RATIOS[int(rng.integers(len(FEAT_RATIOS)))]}
+    imgs = [img]
+    if not sets:
+        if rng.random() < 0.6:
+            dy, dx = (int(v) for v in rng.integers(-6, 7, 2))
+            second = np.roll(img, (dy, dx), axis=(0, 1)).astype(np.int16) + rng.integers(-3, 4, img.shape)
+            imgs.append(np.clip(second, 0, 255).astype(np.uint8))
+            how = f"rolled ({dy},{dx}) + noise"
+        else:
+            imgs.append(feat_image(rng, kind, h, w, cn))
+            how = "independent"
+    desc = (f"FEAT image={kind} size=({w},{h}) cn={'2-D' if p['gray2d'] else cn} scale={p['scale']!r} radius={p['radius']!r} "
+            + " ".join(f"{k}={v}" for k, v in kw.items()))
+    FEAT["drawn"] += 1
+    why = R.refusal(h, w, p["scale"], p["radius"], p["margin"])
+    bad, descs = 0, []
+    for k, im in enumerate(imgs):
+        t = make_view(rng, im, dev, allow_unaligned=True)
+        desc += f" view{k}: contiguous={t.is_contiguous()} byte offset={t.storage_offset()}"
+        if p["gray2d"]:
+            t, im = t[..., 0], im[..., 0]
+        try:
+            got = F.detect(t, radius=p["radius"], scale=p["scale"], **kw)
+        except ValueError:
+            if why is None:
+                raise
+            FEAT["refused"] += 1
+            return desc + f" (refused as predicted: {why})", 0, False
+        if why is not None:
+            return desc + f" (NOT refused; predicted: {why})", 1, True
+        want = R.detect(im, radius=p["radius"], scale=p["scale"], **kw)
+        bad += _differing(got, want)
+        descs.append(want[1])
+        desc += f" n{k}={len(want[0])}"
+    if sets:
+        descs = list(feat_sets(rng))
+        desc += " match on random sets"
+    else:
+        desc += f" second image {how}"
+    na, nb = len(descs[0]), len(descs[1])
+    desc += f" match {na} x {nb} {mkw!r}"
+    got = F.match(descs[0], descs[1], **mkw)
+    want = (R.match_blocked if max(na, nb) > 4096 else R.match)(descs[0], descs[1], **mkw)
+    bad += _differing(got, want)
+    KINDS["feat"] = KINDS.get("feat", 0) + 1
+    return desc + f" matches={len(want[0])}", bad, True
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=300)
@@ -779,6 +933,7 @@ def main() -> int:
     ap.add_argument("--fused", type=float, default=0.06, help="share of cases through v1c_remap_fused by raw ctypes")
     ap.add_argument("--wide", type=float, default=0.0, help="share of cases with uint16 / float32 pixels: the chain cases and the LUT cases (k_remap_wide) against wide_ref.remap")
     ap.add_argument("--png", type=float, default=0.0, help="share of cases through the device PNG encoder (encode_png_tensor) against png_ref.encode")
+    ap.add_argument("--feat", type=float, default=0.0, help="share of cases through the feature pipeline (features.detect / features.match) against tests/feat_ref.py")
     ap.add_argument("--only", type=int, default=None, help="run only this case number (reproduce)")
     ap.add_argument("--log", default=None)
     ap.add_argument("--trace", default=None, help="file that always holds the number of the case being run")
@@ -810,9 +965,12 @@ def main() -> int:
         try:
             r_kind = rng.random()
             wide_chain = False
-            if r_kind >= 1.0 - a.png:  # (the new shares come off the top: with both at 0 every earlier seed replays as it ran)
+            counted = True
+            if r_kind >= 1.0 - a.feat:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+                desc, bad, counted = feat_case(rng, dev)
+            elif r_kind >= 1.0 - a.feat - a.png:
                 desc, bad = png_case(rng, dev)
-            elif r_kind >= 1.0 - a.png - a.wide:
+            elif r_kind >= 1.0 - a.feat - a.png - a.wide:
                 dtype = np.uint16 if rng.random() < 0.5 else np.float32
                 if rng.random() < 0.3:
                     desc, bad = lut_case(rng, dev, dtype)
@@ -832,8 +990,8 @@ def main() -> int:
             else:
                 desc, bad = one_case(rng, dev, a.big)
         except Exception as e:  # noqa: BLE001 -- a refusal of the product (documented limits) is reported, not fatal
-            desc, bad = f"EXCEPTION {type(e).__name__}: {e}", -1
-        n_cases += 1
+            desc, bad, counted = f"EXCEPTION {type(e).__name__}: {e}", -1, True
+        n_cases += 1 if counted else 0
         if wide_chain and bad >= 0:
             WIDE_CHAIN["run"] += 1
             if LAST_MASKED[0] > 0.05:  # mostly masks, little comparison: checked like every case, but not a case of the run's total
@@ -852,7 +1010,8 @@ def main() -> int:
     say(f"fuzz seed {a.seed}: {n_cases} cases in {time.time() - t0:.0f} s, {n_bad} reported; {SINGULAR[0]} differing ill-conditioned pixels left out"
         + (f", {TIES[0]} at float32 rounding ties" if TIES[0] else "")
         + (f"; wide chain cases: {WIDE_CHAIN['run']} run, {WIDE_CHAIN['not counted']} of them over 5 % masked and not counted, "
-           f"{WIDE_CHAIN['masked px']} of {WIDE_CHAIN['px']} pixels masked" if WIDE_CHAIN["run"] else ""))
+           f"{WIDE_CHAIN['masked px']} of {WIDE_CHAIN['px']} pixels masked" if WIDE_CHAIN["run"] else "")
+        + (f"; feat cases: {FEAT['drawn']} drawn, {FEAT['refused']} of them refused as predicted and not counted" if FEAT["drawn"] else ""))
     say("kernel families of the chain cases' launch groups: " + ", ".join(f"{k} x{v}" for k, v in sorted(KINDS.items())))
     return 1 if n_bad else 0
 

@@ -68,6 +68,14 @@ def _device_of(*images: Any) -> torch.device:
     return _device()
 
 
+def resolve_radius(radius: Any, images: Any) -> float:
+    """The image circle's radius for ``params()``: the magnitude of ``get_radius_smart(radius, images)``.  ``"auto"`` on an image
+    circle on black is NEGATIVE (the sign quirk of the reference's ``get_radius``, kept on purpose: in a map it means the 180-degree
+    flip); the qualifying disc is symmetric about the centre, so only the magnitude matters here, and ``v1c_feat_detect`` takes a positive
+    radius only.  An image without a black border raises ``IndexError`` under ``"auto"``, as in ``match_lr``."""
+    return abs(float(get_radius_smart(radius, images)))
+
+
 def _detect_enqueue(t: torch.Tensor, p: FeatParams) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     dev = t.device
     kp = torch.empty((p.max_keypoints, len(KP_FIELDS)), dtype=torch.int32, device=dev)
@@ -105,10 +113,11 @@ def _to_host(*tensors: torch.Tensor) -> list[np.ndarray]:
 
 def detect(image: Any, *, radius: Any, scale: float = 1.0, **overrides: Any) -> tuple[np.ndarray, np.ndarray]:
     """Keypoints and descriptors of one uint8 image: an ``(N, 6)`` int32 array (columns ``KP_FIELDS``, cell-major) and an ``(N, 32)``
-    uint8 array.  ``radius``: the image circle's radius in original pixels, or ``"auto"`` / ``"max"`` (``get_radius_smart``)."""
+    uint8 array.  ``radius``: the image circle's radius in original pixels, or ``"auto"`` / ``"max"`` (``resolve_radius``: the magnitude of
+    what ``get_radius_smart`` gives)."""
     dev = _device_of(image)
     t = _image_tensor(image, dev)
-    p = params(scale, get_radius_smart(radius, [t]), **overrides)
+    p = params(scale, resolve_radius(radius, [t]), **overrides)
     kp, desc, count = _to_host(*_detect_enqueue(t, p))
     n = int(count[0])
     return kp[:n].copy(), desc[:n].copy()
@@ -135,13 +144,14 @@ def match_points_device(image1: Any, image2: Any, *, scale: float = 1, radius: A
     """``calibration_cv.match_points`` on the device: ``(points1, points2, kp1, kp2, matches, image1, image2)`` with the points in
     ORIGINAL pixels (the centre of each keypoint's source block), ``kp1`` / ``kp2`` the keypoint arrays of ``detect``, ``matches`` an
     ``(M, 3)`` int32 array of (index into kp1, index into kp2, Hamming distance) and the images as given.  Both eyes share one radius:
-    ``get_radius_smart(radius, [image1, image2])``, as ``match_lr`` resolves it.  Fewer than 3 matches raise ``ValueError``.
+    ``resolve_radius(radius, [image1, image2])``, the magnitude of what ``match_lr`` resolves from the same arguments.  Fewer than 3
+    matches raise ``ValueError``.
 
     Two synchronisations: the keypoint counts size the match call (``v1c_feat_match`` takes host counts, so that its grid and scratch
     fit the sets), and one copy at the end brings keypoints, pairs, distances and the match count back together."""
     dev = _device_of(image1, image2)
     t1, t2 = _image_tensor(image1, dev), _image_tensor(image2, dev)
-    p = params(scale, get_radius_smart(radius, [t1, t2]))
+    p = params(scale, resolve_radius(radius, [t1, t2]))
     kp1, desc1, c1 = _detect_enqueue(t1, p)
     kp2, desc2, c2 = _detect_enqueue(t2, p)
     n1, n2 = (int(v) for v in torch.cat([c1, c2]).cpu())
