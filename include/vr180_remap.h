@@ -393,6 +393,31 @@ int v1c_png_deflate(int device, void* stream, const void* img, int h, int w, int
                     int band_rows, uint8_t* out_host, uint64_t capacity, v1c_png_band* bands_out, int32_t* n_bands_out,
                     uint64_t* size_out);
 
+/* ---- JPEG encoding of a device image (INTEGRATION.md section 7 states the file; tests/jpg_ref.py restates it) --------------------
+ * Baseline sequential DCT (SOF0), 8-bit, JFIF BT.601 YCbCr in 4:2:0 or 4:4:4 (one component for cn = 1; alpha of cn = 4 is dropped),
+ * the Annex K quantisation tables scaled by the IJG quality rule, the Annex K Huffman tables, restart intervals of restart_mcus MCUs.
+ * A decodable file, not libjpeg's output byte for byte.                                                                           */
+#define V1C_JPEG_444 0
+#define V1C_JPEG_420 2
+#define V1C_JPEG_HEADER_MAX 1024 /* bytes v1c_jpeg_header can write (613 for three components)                                    */
+
+/* Bytes the scan of an (h, w, cn) image can need: every block at its longest (208 bytes), one pad byte per interval, every byte
+ * stuffed, one marker per interval.  Host-only.  0 for invalid arguments.                                                        */
+uint64_t v1c_jpeg_bound(int h, int w, int cn, int subsampling, int restart_mcus);
+
+/* Everything of the file in front of the scan (SOI, APP0, DQT, SOF0, DHT, DRI, SOS) into the HOST buffer `out`; the file is these
+ * bytes, the scan of v1c_jpeg_encode and EOI (0xFF 0xD9).  Host-only.  Returns the number of bytes, or V1C_E_INVALID.           */
+int64_t v1c_jpeg_header(int h, int w, int cn, int quality, int subsampling, int restart_mcus, uint8_t* out, uint64_t capacity);
+
+/* Encodes the device image img ((h, w, cn) uint8 in cv2 channel order, cn 1 / 3 / 4, row pitch in BYTES; pixels and channels dense)
+ * on `stream` and leaves the scan -- the entropy-coded data with its stuffing bytes and RSTm markers -- in out_host (HOST memory of
+ * `capacity` >= v1c_jpeg_bound bytes; page-locked recommended) and its size in *size_out.  The kernels form one chain without a
+ * host step; the call SYNCHRONISES the stream twice: once for the size, once for the scan.  The result is a pure function of the
+ * pixels and the parameters.  V1C_E_INVALID before any device call for cn, quality outside 1 ... 100, subsampling, restart_mcus
+ * outside 1 ... 65535, sizes < 1 or above 65535, NULL pointers, capacity below the bound, pitch < row bytes.                     */
+int v1c_jpeg_encode(int device, void* stream, const void* img, int h, int w, int64_t pitch, int cn, int quality, int subsampling,
+                    int restart_mcus, uint8_t* out_host, uint64_t capacity, uint64_t* size_out);
+
 #ifdef __cplusplus
 }
 #endif

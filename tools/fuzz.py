@@ -7,7 +7,7 @@ and destination views (dword-aligned or not), per-unit rotations, apply_lr pairs
 (v1c_remap_lut) on random float32 maps sprinkled with NaN, infinities, 2^15 / 2^26 / 2^31-scale values and ties of the 1/32 grid.
 
     python3 tools/fuzz.py [--seconds 300] [--seed 1] [--big 0.15] [--lut 0.15] [--hot 0.3] [--gen2 0] [--api 0.1] [--auto 0.06] [--fused 0.06] [--log gpurun_out/fuzz.log]
-                          [--wide 0] [--png 0] [--feat 0]
+                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0]
 
 --wide P: that share of the cases has uint16 or float32 pixels (k_remap_wide): the chain cases above -- same grammar, views, batches, pairs,
 per-unit rotations, graph replays and the same three masks, counted in the same counters -- and the LUT cases (v1c_remap_lut_ex, nothing left
@@ -17,7 +17,9 @@ restatement takes seconds.  A wide chain case whose masks leave out more than 5 
 towards the run's case total (the summary line says how many).  --png P: that share goes through the device PNG encoder
 (encode_png_tensor) -- a remap result as it lies on the device, or a synthetic image of tests/png_cases.py's generators (run planes across the
 kernels' 64-lane steps, 256-byte segments and 64-segment groups, noise, Fibonacci frequencies; gray / BGR / BGRA, 8- and 16-bit) in a random
-view with a random band height and either filter -- against tests/png_ref.py's file, byte for byte.  --feat P: that share goes through the feature
+view with a random band height and either filter -- against tests/png_ref.py's file, byte for byte.  --jpeg P: that share goes through the device JPEG encoder (encode_jpeg_tensor) -- a remap result or a
+random image in a random view, any quality, either subsampling, a random restart interval -- against tests/jpg_ref.py's file, byte for
+byte.  --feat P: that share goes through the feature
 pipeline of --automatch devfm (features.detect / features.match) against tests/feat_ref.py, keypoints, descriptors and matches equal: images of
 six kinds (noise discs, noise, low contrast, polygons and blobs on a gradient, rendered sphere scenes, flat) of 40 ... 700 px in random views,
 scale, radius, margin, threshold, cell, per_cell and the cap drawn off their defaults, the matcher on the descriptors of two detects or on random
@@ -771,6 +773,61 @@ def png_case(rng, dev) -> tuple[str, int]:
     return f"PNG filter={filt} band_rows={rows!r} {desc}", bad
 
 
+def jpeg_case(rng, dev) -> tuple[str, int]:
+    """the device JPEG encoder (encode_jpeg_tensor) against its NumPy restatement (jpg_ref.encode), the file byte for byte: a remap
+    result as it lies on the device (one eye's half of a side-by-side tensor now and then), or a random image -- smooth, noise, flat,
+    hard edges, sparse coefficients; gray / BGR / BGRA -- in a random view; any quality, either subsampling, a random restart interval"""
+    import jpg_cases as JC
+    import jpg_ref as JR
+
+    quality = int(rng.choice([1, 10, 49, 50, 75, 90, 95, 100])) if rng.random() < 0.7 else int(rng.integers(1, 101))
+    sub = "420" if rng.random() < 0.6 else "444"
+    if rng.random() < 0.3:
+        spec, _ = rand_spec(rng)
+        cn = int(rng.choice([3, 3, 1, 4]))
+        wo, ho, hs, ws = (int(v) for v in rng.integers(1, 400, 4))
+        src = rng.integers(0, 256, (hs, ws, cn), dtype=np.uint8)
+        radius = float(rng.uniform(0.3, 1.2) * min(ws, hs) / 2 + 1.0)
+        s_d = torch.from_numpy(src).to(dev)
+        if rng.random() < 0.5:
+            sbs = V.apply_lr_tensors(CS.to_product(spec), s_d, s_d, size_output=(wo, ho), interpolation=int(rng.choice([0, 1, 4])), radius=radius)
+            t = sbs[:, wo:] if rng.random() < 0.5 else sbs
+        else:
+            t = torch.zeros((ho, wo, cn), dtype=s_d.dtype, device=dev)
+            V.remap_tensors(CS.to_product(spec), [s_d], [t], radius=radius, interpolation=int(rng.choice([0, 1, 4])))
+        img = np.ascontiguousarray(t.cpu().numpy())
+        desc = f"remap result {tuple(img.shape)} contiguous={t.is_contiguous()} spec={spec!r} src=({ws},{hs}) radius={radius!r}"
+    else:
+        h, w = (int(v) for v in (rng.integers(1, 40, 2) if rng.random() < 0.4 else rng.integers(1, 300, 2)))
+        cn = int(rng.choice([3, 3, 1, 4]))
+        kind = str(rng.choice(["smooth", "noise", "flat", "edges", "mixed"]))
+        seed = int(rng.integers(0, 1 << 30))
+        if kind == "smooth":
+            img = JC.smooth(h, w, cn, seed)
+        elif kind == "noise":
+            img = JC.noise(h, w, cn, seed)
+        elif kind == "flat":
+            img = np.full((h, w, cn), int(rng.integers(0, 256)), np.uint8)
+        elif kind == "edges":
+            img = (JC.noise((h + 7) // 8, (w + 7) // 8, cn, seed) > 127).astype(np.uint8).repeat(8, 0).repeat(8, 1)[:h, :w] * 255
+            img = np.roll(img, int(rng.integers(0, 8)), axis=1)
+        else:
+            img = np.where(JC.noise(h, w, 1, seed) > 200, JC.noise(h, w, cn, seed + 1), JC.smooth(h, w, cn, seed + 2))
+        img = np.ascontiguousarray(img)
+        t = make_view(rng, img, dev, allow_unaligned=True)
+        desc = f"{kind} {tuple(img.shape)} seed={seed} contiguous={t.is_contiguous()} byte offset={t.storage_offset()}"
+    h, w, cn = img.shape
+    m = 16 if (cn != 1 and sub == "420") else 8
+    nmcu = -(-h // m) * -(-w // m)
+    r = rng.random()
+    restart = None if r < 0.25 else 1 if r < 0.35 else nmcu if r < 0.45 else 65535 if r < 0.5 else int(rng.integers(1, nmcu + 2))
+    got = V.encode_jpeg_tensor(t, quality=quality, subsampling=sub, restart_mcus=restart)
+    want = JR.encode(img, quality, sub, restart)
+    KINDS["jpeg"] = KINDS.get("jpeg", 0) + 1
+    bad = abs(len(got) - len(want)) + sum(a != b for a, b in zip(got, want)) if got != want else 0
+    return f"JPEG quality={quality} subsampling={sub} restart_mcus={restart!r} {desc}", bad
+
+
 FEAT = {"drawn": 0, "refused": 0}  # feat cases drawn / of them refused by v1c_feat_detect as feat_ref.refusal predicts (not counted)
 FEAT_IMAGES = ["disc", "noise", "low", "scene", "sphere", "flat"]
 FEAT_RATIOS = [(3, 4), (1, 1), (1, 2), (0, 1)]
@@ -933,6 +990,7 @@ def main() -> int:
     ap.add_argument("--fused", type=float, default=0.06, help="share of cases through v1c_remap_fused by raw ctypes")
     ap.add_argument("--wide", type=float, default=0.0, help="share of cases with uint16 / float32 pixels: the chain cases and the LUT cases (k_remap_wide) against wide_ref.remap")
     ap.add_argument("--png", type=float, default=0.0, help="share of cases through the device PNG encoder (encode_png_tensor) against png_ref.encode")
+    ap.add_argument("--jpeg", type=float, default=0.0, help="share of cases through the device JPEG encoder (encode_jpeg_tensor) against jpg_ref.encode")
     ap.add_argument("--feat", type=float, default=0.0, help="share of cases through the feature pipeline (features.detect / features.match) against tests/feat_ref.py")
     ap.add_argument("--only", type=int, default=None, help="run only this case number (reproduce)")
     ap.add_argument("--log", default=None)
@@ -970,7 +1028,9 @@ def main() -> int:
                 desc, bad, counted = feat_case(rng, dev)
             elif r_kind >= 1.0 - a.feat - a.png:
                 desc, bad = png_case(rng, dev)
-            elif r_kind >= 1.0 - a.feat - a.png - a.wide:
+            elif r_kind >= 1.0 - a.feat - a.png - a.jpeg:
+                desc, bad = jpeg_case(rng, dev)
+            elif r_kind >= 1.0 - a.feat - a.png - a.jpeg - a.wide:
                 dtype = np.uint16 if rng.random() < 0.5 else np.float32
                 if rng.random() < 0.3:
                     desc, bad = lut_case(rng, dev, dtype)

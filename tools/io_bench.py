@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """End-to-end time of apply_lr with files either side: C2-sized pair (2 x 4096^2 in, 8192 x 4096 out)
-for PNG / JPEG / NPY, per stage -- what a CLI user of the reference waits for.  python3 tools/io_bench.py [size]"""
+for PNG / JPEG / NPY and JPEG through the device encoder, per stage -- what a CLI user of the reference waits for.  python3 tools/io_bench.py [size]"""
 import json
 import sys
 import tempfile
@@ -54,6 +54,15 @@ with tempfile.TemporaryDirectory(dir=(sys.argv[2] if len(sys.argv) > 2 else None
         t_write, _ = timed(lambda: _io.imwrite(out, sbs))
         res["formats"][ext] = {"read_2_files_s": round(t_read, 3), "write_sbs_s": round(t_write, 3), "apply_lr_total_s": round(t_total, 3),
                                "out_file_mb": round(out.stat().st_size / 1e6, 1), "end_to_end_mpx_s": round(2 * n * n / 1e6 / t_total, 1)}
+    # the JPEG result through the device encoder (device_jpeg=True): the same two files in, no host codec on the way out
+    left, right, out = d / "l.jpg", d / "r.jpg", d / "out_dev.jpg"
+    t_total, _ = timed(lambda: V.apply_lr(t, left_path=left, right_path=right, out_path=out, size_output=(n, n), interpolation=1, radius="max",
+                                          device_jpeg=True))
+    sbs_d = torch.from_numpy(np.array(_io.imread(d / "out.png"))).to(dev)
+    t_write, _ = timed(lambda: V.imwrite_jpeg_tensor(out, sbs_d))
+    res["formats"]["jpg_device"] = {"read_2_files_s": res["formats"]["jpg"]["read_2_files_s"], "write_sbs_s": round(t_write, 3),
+                                    "apply_lr_total_s": round(t_total, 3), "out_file_mb": round(out.stat().st_size / 1e6, 1),
+                                    "end_to_end_mpx_s": round(2 * n * n / 1e6 / t_total, 1)}
     # the PNG writers side by side on the SBS result
     sbs = np.array(_io.imread(d / "out.png"))
     from PIL import Image

@@ -1,0 +1,103 @@
+"""Device tensor -> JPEG bytes on the host: the device encoder (jpeg_device.encode_jpeg_tensor) on a C2-sized side-by-side result
+(8192 x 4096 x 3, the remap of a sphere-scene pair) at quality 95, 4:2:0 and 4:4:4, against the path it replaces (``t.cpu().numpy()`` +
+Pillow at the same quality and subsampling).
+
+``--runs`` calls after a warm-up, over rotated copies of the result (as bench.py rotates its buffers), each between two device events
+and inside a host clock; the call ends in a device synchronisation, so the two agree but for the copy of the scan.  One JSON line per
+subsampling; ``--out`` appends them to a file.
+
+    python tools/jpeg_device_bench.py --out profiles/jpeg_device/bench.jsonl
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/jpeg_device_bench.py --runs 2 --device-only     (per-kernel times)
+"""
+from __future__ import annotations
+
+import argparse
+import io
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path[:0] = [str(ROOT), str(ROOT / "tests")]
+
+
+def result(size: int, dev: torch.device) -> torch.Tensor:
+    import sphere_scene as S
+    import vr180_convert_amd as V
+    from vr180_convert_amd.transformer import EquirectangularEncoder, FisheyeDecoder
+
+    src = min(size, 2048)
+    left, right = S.render(src), S.render(src, S.rotation([0.3, 1, 0.2], 4))
+    sbs = V.apply_lr_tensors(EquirectangularEncoder() * FisheyeDecoder("equidistant"), torch.from_numpy(left).to(dev),
+                             torch.from_numpy(right).to(dev), size_output=(size, size), interpolation=1, radius="max")
+    torch.cuda.synchronize()
+    return sbs
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--size", type=int, default=4096, help="output size per eye")
+    ap.add_argument("--runs", type=int, default=20)
+    ap.add_argument("--quality", type=int, default=95)
+    ap.add_argument("--device-only", action="store_true", help="skip the host path (profiler runs)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("jpeg_device_bench needs the MI355X")
+    from PIL import Image
+
+    import vr180_convert_amd as V
+
+    dev = torch.device("cuda", 0)
+    sbs = result(a.size, dev)
+    copies = [sbs.clone() for _ in range(3)]
+    h, w, cn = (int(v) for v in sbs.shape)
+    for sub in ("420", "444"):
+        def device_path(t):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            data = V.encode_jpeg_tensor(t, quality=a.quality, subsampling=sub)
+            e1.record()
+            e1.synchronize()
+            return data, {"events_ms": e0.elapsed_time(e1), "host_ms": 1e3 * (time.perf_counter() - t0)}
+
+        def host_path(t):
+            t0 = time.perf_counter()
+            host = t.cpu().numpy()
+            t1 = time.perf_counter()
+            b = io.BytesIO()
+            Image.fromarray(np.ascontiguousarray(host[..., ::-1])).save(b, "JPEG", quality=a.quality, subsampling={"420": 2, "444": 0}[sub])
+            t2 = time.perf_counter()
+            return b.getvalue(), {"copy_ms": 1e3 * (t1 - t0), "encode_ms": 1e3 * (t2 - t1), "total_ms": 1e3 * (t2 - t0)}
+
+        jpg_d, _ = device_path(copies[0])  # warm-up: code objects, the page-locked buffer, the memory pool
+        jpg_h = None if a.device_only else host_path(copies[0])[0]
+        torch.cuda.synchronize()
+        drun, hrun = [], []
+        for k in range(a.runs):
+            drun.append(device_path(copies[k % 3])[1])
+            if not a.device_only and k < 3:
+                hrun.append(host_path(copies[k % 3])[1])
+        dec = np.asarray(Image.open(io.BytesIO(jpg_d)))[..., ::-1].astype(np.float64)
+        mse = float(np.mean((dec - sbs.cpu().numpy()) ** 2))
+        ev = sorted(r["events_ms"] for r in drun)
+        line = {"shape": [h, w, cn], "quality": a.quality, "subsampling": sub, "runs": a.runs, "raw_bytes": h * w * cn,
+                "device_jpeg_bytes": len(jpg_d), "host_jpeg_bytes": None if jpg_h is None else len(jpg_h),
+                "psnr_db": round(10 * np.log10(255.0 ** 2 / max(mse, 1e-12)), 2),
+                "events_ms_min_median_max": [round(ev[0], 3), round(ev[len(ev) // 2], 3), round(ev[-1], 3)],
+                "mpixel_per_s_median": round(h * w / 1e3 / ev[len(ev) // 2], 1), "device": drun, "host": hrun}
+        text = json.dumps(line)
+        print(text, flush=True)
+        if a.out:
+            Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

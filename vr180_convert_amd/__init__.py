@@ -19,6 +19,7 @@ from .remapper import (anaglyph_tensors, apply, apply_lr, apply_lr_tensors, auto
                        remap_tensors_auto)
 from .features import detect, match, match_points_device
 from .png_device import encode_png_tensor, imwrite_tensor
+from .jpeg_device import encode_jpeg_tensor, imwrite_jpeg_tensor
 from .sharding import remap_sharded
 
 __all__ = [
@@ -50,4 +51,7 @@ __all__ = [
     # PNG files of device-resident results, deflated on the device (device_png=True / --device-png)
     "encode_png_tensor",
     "imwrite_tensor",
+    # JPEG files of device-resident results, encoded on the device (device_jpeg=True / --device-jpeg)
+    "encode_jpeg_tensor",
+    "imwrite_jpeg_tensor",
 ]

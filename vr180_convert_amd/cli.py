@@ -212,6 +212,8 @@ def lr(
     savematch: Annotated[bool, typer.Option(help="Save the match image <out>.match<ext> (only with automatch=fm)")] = False,
     device_png: Annotated[bool, typer.Option("--device-png", help="Deflate .png results on the GPU (larger files, no host codec "
                                                                    "time); other formats and --merge are written by the host")] = False,
+    device_jpeg: Annotated[bool, typer.Option("--device-jpeg", help="Encode .jpg / .jpeg results on the GPU (baseline JPEG, quality 95, "
+                                                                     "4:2:0); other formats and --merge are written by the host")] = False,
 ) -> None:
     """Remap a pair of fisheye images to a pair of SBS equirectangular images."""
     from .remapper import apply_lr
@@ -239,7 +241,7 @@ def lr(
         LOG.info(f"Automatched transformer: {chain}")
     apply_lr(chain, left_path=left_path, right_path=right_path, out_path=out, radius=radius_, size_output=parse_size(size),
              interpolation=interp, boarder_mode=border, boarder_value=border_value, merge=merge,
-             **({"device_png": True} if device_png else {}))
+             **({"device_png": True} if device_png else {}), **({"device_jpeg": True} if device_jpeg else {}))
 
 
 @app.command()
@@ -254,6 +256,8 @@ def s(
     radius: Annotated[str, typer.Option(help="Radius of the fisheye image: a number, 'auto' or 'max'")] = "auto",
     device_png: Annotated[bool, typer.Option("--device-png", help="Deflate .png results on the GPU (larger files, no host codec "
                                                                    "time); other formats and --merge are written by the host")] = False,
+    device_jpeg: Annotated[bool, typer.Option("--device-jpeg", help="Encode .jpg / .jpeg results on the GPU (baseline JPEG, quality 95, "
+                                                                     "4:2:0); other formats are written by the host")] = False,
 ) -> None:
     """Remap fisheye images to equirectangular images (one shared map for all of them)."""
     from .remapper import apply
@@ -269,7 +273,7 @@ def s(
     apply(parse_transformer(transformer), in_paths=list(in_paths), out_paths=out_paths, radius=parse_radius(radius),
           size_output=parse_size(size), interpolation=_flag(interpolation, _INTERPOLATIONS, "inter_", "interpolation"),
           boarder_mode=_flag(boarder_mode, _BORDERS, "border_", "border mode"), boarder_value=boarder_value,
-          **({"device_png": True} if device_png else {}))
+          **({"device_png": True} if device_png else {}), **({"device_jpeg": True} if device_jpeg else {}))
 
 
 @app.command()

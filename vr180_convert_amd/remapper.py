@@ -687,6 +687,7 @@ def apply(
     radius: float | Literal["auto", "max"] = "auto",
     device: Any = None,
     device_png: bool = False,
+    device_jpeg: bool = False,
 ) -> Sequence[NDArray[np.uint8]]:
     """Apply transformer to images (reference remapper.py:324-403).
 
@@ -736,13 +737,20 @@ def apply(
         results = [r[..., 0] if np.asarray(im).ndim == 2 else r for r, im in zip(results, images)]
     if out_paths_ is not None:
         paths = list(out_paths_)[: len(results)]
-        if device_png:
-            from . import png_device
+        if device_png or device_jpeg:
+            writers = []  # .png / .jpg results still on the device are encoded there (png_device.py, jpeg_device.py)
+            if device_png:
+                from . import png_device
 
-            on_dev = [png_device.eligible(q, d) for q, d in zip(paths, dsts)]
-            for q, d, ok in zip(paths, dsts, on_dev):
-                if ok:
-                    png_device.imwrite_tensor(q, d)
+                writers.append((png_device.eligible, png_device.imwrite_tensor))
+            if device_jpeg:
+                from . import jpeg_device
+
+                writers.append((jpeg_device.eligible, jpeg_device.imwrite_jpeg_tensor))
+            on_dev = [next((write for ok, write in writers if ok(q, d)), None) for q, d in zip(paths, dsts)]
+            for q, d, write in zip(paths, dsts, on_dev):
+                if write:
+                    write(q, d)
             keep = [i for i, ok in enumerate(on_dev) if not ok]
             paths, results_ = [paths[i] for i in keep], [results[i] for i in keep]
         else:
@@ -951,12 +959,15 @@ def apply_lr(
     merge: bool = False,
     device: Any = None,
     device_png: bool = False,
+    device_jpeg: bool = False,
 ) -> None:
     """Apply transformer to a pair of images and save them side by side (reference
     remapper.py:406-520).  ``left_path == right_path`` means one file holding both eyes.
 
     ``device_png=True``: a ``.png`` ``out_path`` of a uint8 / uint16 side-by-side result is deflated on the device
-    (png_device.imwrite_tensor) and the raw result is not copied to the host; ``merge=True`` and other formats take the host route."""
+    (png_device.imwrite_tensor) and the raw result is not copied to the host; ``merge=True`` and other formats take the host route.
+    ``device_jpeg=True``: the same for a ``.jpg`` / ``.jpeg`` ``out_path`` of a uint8 result (jpeg_device.imwrite_jpeg_tensor:
+    quality 95, 4:2:0, as the host writer)."""
     if isinstance(left_path, (str, Path)) and isinstance(right_path, (str, Path)) and left_path == right_path:
         image = _io.imread(left_path)
         left_path = image[:, : image.shape[1] // 2]
@@ -990,6 +1001,13 @@ def apply_lr(
 
             if png_device.eligible(out_path, sbs):
                 png_device.imwrite_tensor(out_path, sbs)
+                LOG.info(f"Saved to {Path(out_path).absolute()}")
+                return
+        if device_jpeg and out_path is not None:
+            from . import jpeg_device
+
+            if jpeg_device.eligible(out_path, sbs):
+                jpeg_device.imwrite_jpeg_tensor(out_path, sbs)
                 LOG.info(f"Saved to {Path(out_path).absolute()}")
                 return
         combine = sbs.cpu().numpy()
