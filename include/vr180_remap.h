@@ -36,6 +36,7 @@ extern "C" {
                                   to v1c_remap_lut with a map it computed itself)           */
 #define V1C_E_HIP         -3   /* a HIP runtime call failed (message has hipGetErrorString)  */
 #define V1C_E_NODEVICE    -4   /* no usable gfx950 device                                    */
+#define V1C_E_CORRUPT     -5   /* the input data is damaged (v1c_jpeg_decode*)               */
 
 /* ---- cv2 enum values the reference passes straight through ---------------------------
  * remapper.py:330-331 (defaults INTER_LANCZOS4 / BORDER_CONSTANT), cli.py:57-79 (mirrors). */
@@ -417,6 +418,42 @@ int64_t v1c_jpeg_header(int h, int w, int cn, int quality, int subsampling, int 
  * outside 1 ... 65535, sizes < 1 or above 65535, NULL pointers, capacity below the bound, pitch < row bytes.                     */
 int v1c_jpeg_encode(int device, void* stream, const void* img, int h, int w, int64_t pitch, int cn, int quality, int subsampling,
                     int restart_mcus, uint8_t* out_host, uint64_t capacity, uint64_t* size_out);
+
+/* ---- JPEG decoding into a device image (INTEGRATION.md section 8 states the contract; tests/jpgdec_ref.py restates it) ------------
+ * Sequential DCT with Huffman coding and 8-bit samples (SOF0, SOF1) in one interleaved scan: one component, or three as JFIF YCbCr
+ * in 4:4:4, 4:2:2 or 4:2:0; any DQT, DHT and DRI.  Everything else a JPEG file may be -- progressive, lossless, arithmetic, 12-bit,
+ * several scans, DNL, other sampling factors, four components, Adobe transform 0 -- is V1C_E_UNSUPPORTED from a host-only parse,
+ * a damaged file V1C_E_CORRUPT.  The Huffman decoding is parallel over subsequences of the unstuffed scan whose entry states are
+ * found by iteration; the pixels follow libjpeg's default decoder (accurate integer IDCT, triangle-filter upsampling).           */
+typedef struct v1c_jpeg_info {
+    int32_t height, width;
+    int32_t components;        /* 1 or 3                                                                                          */
+    int32_t h_samp, v_samp;    /* luma sampling factors: 1x1 (grey, 4:4:4), 2x1 (4:2:2), 2x2 (4:2:0)                              */
+    int32_t restart_interval;  /* MCUs; 0: none                                                                                   */
+} v1c_jpeg_info;
+
+typedef struct v1c_jpeg_decode_report {
+    uint32_t segments;         /* stretches of the scan between restart markers                                                   */
+    uint32_t subsequences;     /* lanes of the parallel decode                                                                    */
+    uint32_t rounds;           /* launches until no subsequence's entry state changed                                             */
+    uint32_t reserved;
+    uint64_t error_pos;        /* V1C_E_CORRUPT / V1C_E_UNSUPPORTED: byte of the file where the parse stopped, or bit of the
+                                  unstuffed scan where decoding did                                                               */
+} v1c_jpeg_decode_report;
+
+/* Host-only parse of a file of `size` bytes in HOST memory: the markers and one walk over the scan's 0xFF bytes.  Touches no device.
+ * V1C_E_INVALID for NULL pointers, else V1C_OK, V1C_E_UNSUPPORTED or V1C_E_CORRUPT (what a parse can tell; a damaged entropy-coded
+ * segment shows only in v1c_jpeg_decode).                                                                                        */
+int v1c_jpeg_decode_info(const uint8_t* file, uint64_t size, v1c_jpeg_info* info);
+
+/* Decodes the file into the device image out ((height, width, out_cn) uint8, cv2 channel order, row pitch in BYTES): out_cn 3, or 1
+ * for a file of one component (which out_cn 3 replicates).  The scan is uploaded from a page-locked staging buffer on `stream`.
+ * subseq_bits: bits of the unstuffed scan one lane decodes -- a multiple of 32, at least 256, 0 for the default; the pixels do not
+ * depend on it.  The call SYNCHRONISES the stream once per round and once for the verdict on the stream, and returns with the
+ * remaining kernels queued; it cannot be captured into a graph (V1C_E_UNSUPPORTED under capture).  `report` may be NULL.  After
+ * V1C_E_CORRUPT the image's content is unspecified.  No read leaves the uploaded data and its padding whatever the file holds.  */
+int v1c_jpeg_decode(int device, void* stream, const uint8_t* file, uint64_t size, void* out, int64_t pitch, int out_cn,
+                    uint32_t subseq_bits, v1c_jpeg_decode_report* report);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,7 @@ and destination views (dword-aligned or not), per-unit rotations, apply_lr pairs
 (v1c_remap_lut) on random float32 maps sprinkled with NaN, infinities, 2^15 / 2^26 / 2^31-scale values and ties of the 1/32 grid.
 
     python3 tools/fuzz.py [--seconds 300] [--seed 1] [--big 0.15] [--lut 0.15] [--hot 0.3] [--gen2 0] [--api 0.1] [--auto 0.06] [--fused 0.06] [--log gpurun_out/fuzz.log]
-                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0]
+                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--cases N]
 
 --wide P: that share of the cases has uint16 or float32 pixels (k_remap_wide): the chain cases above -- same grammar, views, batches, pairs,
 per-unit rotations, graph replays and the same three masks, counted in the same counters -- and the LUT cases (v1c_remap_lut_ex, nothing left
@@ -19,7 +19,9 @@ towards the run's case total (the summary line says how many).  --png P: that sh
 kernels' 64-lane steps, 256-byte segments and 64-segment groups, noise, Fibonacci frequencies; gray / BGR / BGRA, 8- and 16-bit) in a random
 view with a random band height and either filter -- against tests/png_ref.py's file, byte for byte.  --jpeg P: that share goes through the device JPEG encoder (encode_jpeg_tensor) -- a remap result or a
 random image in a random view, any quality, either subsampling, a random restart interval -- against tests/jpg_ref.py's file, byte for
-byte.  --feat P: that share goes through the feature
+byte.  --jpegdec P: that share goes through the device JPEG decoder (decode_jpeg_tensor) -- a random image up to 96 x 96 written by Pillow or
+by tests/jpg_ref.py with random sampling, quality, restart setting and optimised tables, at a random subsequence size -- against
+tests/jpgdec_ref.py's pixels, byte for byte.  --feat P: that share goes through the feature
 pipeline of --automatch devfm (features.detect / features.match) against tests/feat_ref.py, keypoints, descriptors and matches equal: images of
 six kinds (noise discs, noise, low contrast, polygons and blobs on a gradient, rendered sphere scenes, flat) of 40 ... 700 px in random views,
 scale, radius, margin, threshold, cell, per_cell and the cap drawn off their defaults, the matcher on the descriptors of two detects or on random
@@ -828,6 +830,60 @@ def jpeg_case(rng, dev) -> tuple[str, int]:
     return f"JPEG quality={quality} subsampling={sub} restart_mcus={restart!r} {desc}", bad
 
 
+def jpegdec_case(rng, dev) -> tuple[str, int]:
+    """the device JPEG decoder (decode_jpeg_tensor) against its restatement (jpgdec_ref.decode), the pixels byte for byte: a random
+    image up to 96 x 96 -- smooth, noise, flat, mixed -- written by Pillow (grey, 4:4:4, 4:2:2 or 4:2:0, any quality, optimised tables
+    and its restart options now and then) or by the encoder's restatement (any restart interval), decoded at a random subsequence size"""
+    import jpg_cases as JC
+    import jpg_ref as JR
+    import jpgdec_cases as DC
+    import jpgdec_ref as DR
+
+    h, w = (int(v) for v in rng.integers(1, 97, 2))
+    quality = int(rng.choice([1, 10, 50, 75, 90, 95, 100])) if rng.random() < 0.7 else int(rng.integers(1, 101))
+    kind = str(rng.choice(["smooth", "noise", "flat", "mixed"]))
+    seed = int(rng.integers(0, 1 << 30))
+    cn = 1 if rng.random() < 0.2 else 3
+    if kind == "smooth":
+        img = JC.smooth(h, w, cn, seed)
+    elif kind == "noise":
+        img = JC.noise(h, w, cn, seed)
+    elif kind == "flat":
+        img = np.full((h, w, cn), int(rng.integers(0, 256)), np.uint8)
+    else:
+        img = np.where(JC.noise(h, w, 1, seed) > 200, JC.noise(h, w, cn, seed + 1), JC.smooth(h, w, cn, seed + 2))
+    img = np.ascontiguousarray(img)
+    if rng.random() < 0.3:
+        sampling = "420" if rng.random() < 0.6 else "444"
+        m = 16 if (cn != 1 and sampling == "420") else 8
+        nmcu = -(-h // m) * -(-w // m)
+        r = rng.random()
+        restart = 1 if r < 0.2 else nmcu if r < 0.3 else 65535 if r < 0.4 else int(rng.integers(1, nmcu + 2))
+        data = JR.encode(img, quality, sampling, restart)
+        how = f"jpg_ref restart_mcus={restart}"
+    else:
+        sampling = str(rng.choice(["444", "422", "420"]))
+        kw = {}
+        if rng.random() < 0.3:
+            kw["optimize"] = True
+        r = rng.random()
+        if r < 0.2:
+            kw["restart_marker_blocks"] = int(rng.integers(1, 12))
+        elif r < 0.35:
+            kw["restart_marker_rows"] = int(rng.integers(1, 4))
+        data = DC.pillow(img, quality, sampling, **kw)
+        how = f"Pillow {kw!r}"
+    S = int(rng.choice([0, 256, 256, 288, 512, 1024, 4096]))
+    channels = 1 if cn == 1 and rng.random() < 0.5 else 3
+    got = V.decode_jpeg_tensor(data, channels=channels, subseq_bits=S or None).cpu().numpy()
+    rep = V.last_decode_report()
+    want = DR.decode(data, S, channels=channels, check=False)
+    KINDS["jpegdec"] = KINDS.get("jpegdec", 0) + 1
+    bad = int((got != want.pixels).sum()) if got.shape == want.pixels.shape else got.size
+    bad += 0 if (rep["segments"], rep["subsequences"]) == (want.segments, want.subsequences) and rep["rounds"] <= want.rounds else 1
+    return f"JPEGDEC {kind} {(h, w, cn)} seed={seed} quality={quality} sampling={sampling} {how} subseq_bits={S} channels={channels}", bad
+
+
 FEAT = {"drawn": 0, "refused": 0}  # feat cases drawn / of them refused by v1c_feat_detect as feat_ref.refusal predicts (not counted)
 FEAT_IMAGES = ["disc", "noise", "low", "scene", "sphere", "flat"]
 FEAT_RATIOS = [(3, 4), (1, 1), (1, 2), (0, 1)]
@@ -991,6 +1047,8 @@ def main() -> int:
     ap.add_argument("--wide", type=float, default=0.0, help="share of cases with uint16 / float32 pixels: the chain cases and the LUT cases (k_remap_wide) against wide_ref.remap")
     ap.add_argument("--png", type=float, default=0.0, help="share of cases through the device PNG encoder (encode_png_tensor) against png_ref.encode")
     ap.add_argument("--jpeg", type=float, default=0.0, help="share of cases through the device JPEG encoder (encode_jpeg_tensor) against jpg_ref.encode")
+    ap.add_argument("--jpegdec", type=float, default=0.0, help="share of cases through the device JPEG decoder (decode_jpeg_tensor) against jpgdec_ref.decode")
+    ap.add_argument("--cases", type=int, default=None, help="stop after this many cases (before --seconds runs out)")
     ap.add_argument("--feat", type=float, default=0.0, help="share of cases through the feature pipeline (features.detect / features.match) against tests/feat_ref.py")
     ap.add_argument("--only", type=int, default=None, help="run only this case number (reproduce)")
     ap.add_argument("--log", default=None)
@@ -1013,7 +1071,7 @@ def main() -> int:
     n_cases = n_bad = 0
     last = t0
     case = 0
-    while time.time() - t0 < a.seconds:
+    while time.time() - t0 < a.seconds and (a.cases is None or case < a.cases):
         rng = np.random.default_rng([a.seed, case])  # every case reproducible by itself
         if a.only is not None:
             rng = np.random.default_rng([a.seed, a.only])
@@ -1024,13 +1082,16 @@ def main() -> int:
             r_kind = rng.random()
             wide_chain = False
             counted = True
-            if r_kind >= 1.0 - a.feat:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+            top = 1.0 - a.jpegdec
+            if r_kind >= top:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+                desc, bad = jpegdec_case(rng, dev)
+            elif r_kind >= top - a.feat:
                 desc, bad, counted = feat_case(rng, dev)
-            elif r_kind >= 1.0 - a.feat - a.png:
+            elif r_kind >= top - a.feat - a.png:
                 desc, bad = png_case(rng, dev)
-            elif r_kind >= 1.0 - a.feat - a.png - a.jpeg:
+            elif r_kind >= top - a.feat - a.png - a.jpeg:
                 desc, bad = jpeg_case(rng, dev)
-            elif r_kind >= 1.0 - a.feat - a.png - a.jpeg - a.wide:
+            elif r_kind >= top - a.feat - a.png - a.jpeg - a.wide:
                 dtype = np.uint16 if rng.random() < 0.5 else np.float32
                 if rng.random() < 0.3:
                     desc, bad = lut_case(rng, dev, dtype)

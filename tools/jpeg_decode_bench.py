@@ -1,0 +1,108 @@
+"""JPEG file bytes -> device tensor: the device decoder (jpeg_decode_device.decode_jpeg_tensor) against the path it replaces (Pillow on
+the host + the upload of the decoded frame), for the given files or, without any, for tests/golden/ref_docs/test.jpg (2048 x 2048,
+4:2:0, one entropy-coded segment) and a 4096 x 4096 4:2:0 quality-95 file written by Pillow from the sphere scene.
+
+For every file the host-only parse is timed by itself (it is part of every call); for every file and every ``--subseq-bits`` value:
+``--runs`` calls after a warm-up, each between two device events and inside a host
+clock, the synchronisation rounds the call took and the subsequences it ran over; Pillow's decode and the upload three times.  One
+JSON line per (file, subseq_bits); ``--out`` appends them to a file.
+
+    python tools/jpeg_decode_bench.py --subseq-bits 512 1024 2048 4096 --out profiles/jpeg_decode/bench.jsonl
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/jpeg_decode_bench.py --runs 2 --device-only     (per-kernel times)
+"""
+from __future__ import annotations
+
+import argparse
+import io
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path[:0] = [str(ROOT), str(ROOT / "tests")]
+
+
+def default_files() -> dict:
+    import sphere_scene as S
+    from PIL import Image
+
+    big = np.kron(S.render(2048), np.ones((2, 2, 1), np.uint8))  # 4096 x 4096: the scene at twice the size
+    big = (big.astype(np.int16) + np.random.default_rng(0).integers(-6, 7, big.shape, dtype=np.int16)).clip(0, 255).astype(np.uint8)
+    b = io.BytesIO()
+    Image.fromarray(np.ascontiguousarray(big[..., ::-1])).save(b, "JPEG", quality=95, subsampling=2)
+    return {"docs_2048": (ROOT / "tests" / "golden" / "ref_docs" / "test.jpg").read_bytes(), "sphere_4096_q95_420": b.getvalue()}
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("files", nargs="*", help="JPEG files (default: the docs image and a 4096 x 4096 sphere scene)")
+    ap.add_argument("--subseq-bits", type=int, nargs="+", default=[0], help="0: the engine's default")
+    ap.add_argument("--runs", type=int, default=10)
+    ap.add_argument("--device-only", action="store_true", help="skip the host path (profiler runs)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("jpeg_decode_bench needs the MI355X")
+    from PIL import Image
+
+    import vr180_convert_amd as V
+
+    dev = torch.device("cuda", 0)
+    files = {Path(f).name: Path(f).read_bytes() for f in a.files} if a.files else default_files()
+    for name, data in files.items():
+        host = []
+        ref = None
+        for _ in range(0 if a.device_only else 3):
+            t0 = time.perf_counter()
+            arr = np.ascontiguousarray(np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))[..., ::-1])
+            t1 = time.perf_counter()
+            torch.from_numpy(arr).to(dev)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            host.append({"decode_ms": 1e3 * (t1 - t0), "upload_ms": 1e3 * (t2 - t1), "total_ms": 1e3 * (t2 - t0)})
+            ref = arr
+        # the host-only parse by itself (markers and the memchr walk over the scan): it runs twice per decode_jpeg_tensor call, once to
+        # size the tensor and once inside v1c_jpeg_decode, and both lie inside host_ms below
+        from vr180_convert_amd import jpeg_decode_device as J
+
+        parse = []
+        for _ in range(max(a.runs, 3)):
+            t0 = time.perf_counter()
+            J.probe(data)
+            parse.append(1e3 * (time.perf_counter() - t0))
+        parse.sort()
+        for S in a.subseq_bits:
+            kw = {} if S == 0 else {"subseq_bits": S}
+            out = V.decode_jpeg_tensor(data, **kw)  # warm-up: code objects, the staging buffer, the memory pool
+            torch.cuda.synchronize()
+            rep = V.last_decode_report()
+            runs = []
+            for _ in range(a.runs):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0 = time.perf_counter()
+                e0.record()
+                out = V.decode_jpeg_tensor(data, **kw)
+                e1.record()
+                e1.synchronize()
+                runs.append({"events_ms": e0.elapsed_time(e1), "host_ms": 1e3 * (time.perf_counter() - t0)})
+            ev = sorted(r["events_ms"] for r in runs)
+            h, w = int(out.shape[0]), int(out.shape[1])
+            line = {"file": name, "bytes": len(data), "shape": [h, w, 3], "subseq_bits": S, "runs": a.runs, **rep,
+                    "host_parse_ms_min_median": [round(parse[0], 4), round(parse[len(parse) // 2], 4)],
+                    "equals_pillow": None if ref is None else bool(np.array_equal(out.cpu().numpy(), ref)),
+                    "events_ms_min_median_max": [round(ev[0], 3), round(ev[len(ev) // 2], 3), round(ev[-1], 3)],
+                    "mpixel_per_s_median": round(h * w / 1e3 / ev[len(ev) // 2], 1), "device": runs, "host": host}
+            text = json.dumps(line)
+            print(text, flush=True)
+            if a.out:
+                Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+                with open(a.out, "a") as f:
+                    f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

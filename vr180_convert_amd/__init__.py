@@ -20,6 +20,7 @@ from .remapper import (anaglyph_tensors, apply, apply_lr, apply_lr_tensors, auto
 from .features import detect, match, match_points_device
 from .png_device import encode_png_tensor, imwrite_tensor
 from .jpeg_device import encode_jpeg_tensor, imwrite_jpeg_tensor
+from .jpeg_decode_device import decode_jpeg_tensor, imread_tensor, last_decode_report
 from .sharding import remap_sharded
 
 __all__ = [
@@ -54,4 +55,8 @@ __all__ = [
     # JPEG files of device-resident results, encoded on the device (device_jpeg=True / --device-jpeg)
     "encode_jpeg_tensor",
     "imwrite_jpeg_tensor",
+    # JPEG inputs decoded on the device into tensors (device_decode=True / --device-decode)
+    "decode_jpeg_tensor",
+    "imread_tensor",
+    "last_decode_report",
 ]

@@ -8,7 +8,7 @@ ABI_VERSION = 1
 MAX_OPS = 16
 MAX_PARAMS = 16
 
-OK, E_INVALID, E_UNSUPPORTED, E_HIP, E_NODEVICE = 0, -1, -2, -3, -4
+OK, E_INVALID, E_UNSUPPORTED, E_HIP, E_NODEVICE, E_CORRUPT = 0, -1, -2, -3, -4, -5
 
 # cv2 enum values (reference cli.py:57-79 mirrors the same names)
 INTER_NEAREST, INTER_LINEAR, INTER_CUBIC, INTER_AREA, INTER_LANCZOS4 = 0, 1, 2, 3, 4

@@ -5,7 +5,9 @@ BGR like cv2's.  Codec work is outside the measured path.
 Two additions for batch work, where codecs -- not the remap -- set the end-to-end time:
 * ``.npy`` files are read (memory-mapped) as raw uint8 arrays and written as raw uint8 / uint16 / float32 arrays (anything else
   saturated to uint8, as before) in cv2 channel order: the codec-free
-  format for frame sequences (the GPU image ships no device-side JPEG / PNG codec: no rocJPEG, no torchvision);
+  format for frame sequences (the GPU image ships no rocJPEG and no torchvision; the engine's own device codecs -- png_device.py,
+  jpeg_device.py and, for baseline JPEG inputs, jpeg_decode_device.py -- are opt-in through ``device_png`` / ``device_jpeg`` /
+  ``device_decode``);
 * large PNGs are written by the multi-threaded encoder of ``_png.py`` when cv2 is absent, and PNGs it wrote are read back by its
   multi-threaded decoder (a private chunk holds the band directory; every other reader sees an ordinary PNG);
 * uint16 results written to ``.png`` become 16-bit PNGs, as with cv2.imwrite; float32 results and other formats are saturated to

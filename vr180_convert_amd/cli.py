@@ -126,7 +126,7 @@ def _option_number(automatch: str, prefix: str, pattern: str, default: float) ->
     return float(m.group(1)) if m and m.group(1) else default
 
 
-def calibrated_pair(transformer: Any, automatch: str, left: Path, right: Path, radius: Any, match_image_path: Optional[Path] = None) -> tuple[Any, Any]:
+def calibrated_pair(transformer: Any, automatch: str, left: Any, right: Any, radius: Any, match_image_path: Optional[Path] = None) -> tuple[Any, Any]:
     """``--automatch``: estimate the rotation between the eyes from matched points and give each eye half of it
     (cli.py:234-319): (left chain, right chain).  The points come from the option itself (``"xl,yl;xr,yr;..."``: even entries the
     left eye, odd entries the right; plain least-squares fit ``rotation_match``), from clicks (``gui[n]``: n pairs, default 2) or from
@@ -141,7 +141,9 @@ def calibrated_pair(transformer: Any, automatch: str, left: Path, right: Path, r
         scale = _option_number(automatch, "devfm", r"([\d\.]+)", 1)
         if not 0 < scale <= 1:
             raise typer.BadParameter(f"--automatch {automatch}: the working scale must lie in (0, 1], e.g. devfm0.5")
-        matched = _feat.match_points_device(_io.imread(left), _io.imread(right), scale=scale, radius=radius)
+        # (--device-decode hands over the decoded tensors: the matcher takes them where they lie)
+        images = [_io.imread(q) if isinstance(q, (str, Path)) else q for q in (left, right)]
+        matched = _feat.match_points_device(images[0], images[1], scale=scale, radius=radius)
         points_l, points_r = matched[0], matched[1]
     elif automatch.startswith("fm") or automatch.startswith("gui"):
         from . import calibration_cv as _cvx
@@ -214,6 +216,8 @@ def lr(
                                                                    "time); other formats and --merge are written by the host")] = False,
     device_jpeg: Annotated[bool, typer.Option("--device-jpeg", help="Encode .jpg / .jpeg results on the GPU (baseline JPEG, quality 95, "
                                                                      "4:2:0); other formats and --merge are written by the host")] = False,
+    device_decode: Annotated[bool, typer.Option("--device-decode", help="Decode .jpg / .jpeg inputs on the GPU (baseline JPEG; other "
+                                                                         "files are read by the host)")] = False,
 ) -> None:
     """Remap a pair of fisheye images to a pair of SBS equirectangular images."""
     from .remapper import apply_lr
@@ -235,13 +239,21 @@ def lr(
     if savematch and not automatch.startswith("fm"):
         # (the reference ignores the flag silently, cli.py:365: scripts that always pass it keep working)
         LOG.warning("--savematch ignored: it draws the feature matches of --automatch fm, and there are none without it")
+    left_in: Any = left_path
+    right_in: Any = right_path
+    if device_decode and automatch.startswith("devfm") and left_path != right_path:
+        # decoded once, here: the matcher and apply_lr both take the tensors (apply_lr passes what is no path through)
+        from . import jpeg_decode_device
+
+        left_in, right_in = jpeg_decode_device.read_inputs([left_path, right_path])
     if automatch != "":
         match_image = out.with_suffix(f".match{out.suffix}") if savematch else None  # cli.py:362-365
-        chain = calibrated_pair(chain, automatch, left_path, right_path, radius_, match_image)
+        chain = calibrated_pair(chain, automatch, left_in, right_in, radius_, match_image)
         LOG.info(f"Automatched transformer: {chain}")
-    apply_lr(chain, left_path=left_path, right_path=right_path, out_path=out, radius=radius_, size_output=parse_size(size),
+    apply_lr(chain, left_path=left_in, right_path=right_in, out_path=out, radius=radius_, size_output=parse_size(size),
              interpolation=interp, boarder_mode=border, boarder_value=border_value, merge=merge,
-             **({"device_png": True} if device_png else {}), **({"device_jpeg": True} if device_jpeg else {}))
+             **({"device_png": True} if device_png else {}), **({"device_jpeg": True} if device_jpeg else {}),
+             **({"device_decode": True} if device_decode else {}))
 
 
 @app.command()
@@ -258,6 +270,8 @@ def s(
                                                                    "time); other formats and --merge are written by the host")] = False,
     device_jpeg: Annotated[bool, typer.Option("--device-jpeg", help="Encode .jpg / .jpeg results on the GPU (baseline JPEG, quality 95, "
                                                                      "4:2:0); other formats are written by the host")] = False,
+    device_decode: Annotated[bool, typer.Option("--device-decode", help="Decode .jpg / .jpeg inputs on the GPU (baseline JPEG; other "
+                                                                         "files are read by the host)")] = False,
 ) -> None:
     """Remap fisheye images to equirectangular images (one shared map for all of them)."""
     from .remapper import apply
@@ -273,7 +287,8 @@ def s(
     apply(parse_transformer(transformer), in_paths=list(in_paths), out_paths=out_paths, radius=parse_radius(radius),
           size_output=parse_size(size), interpolation=_flag(interpolation, _INTERPOLATIONS, "inter_", "interpolation"),
           boarder_mode=_flag(boarder_mode, _BORDERS, "border_", "border mode"), boarder_value=boarder_value,
-          **({"device_png": True} if device_png else {}), **({"device_jpeg": True} if device_jpeg else {}))
+          **({"device_png": True} if device_png else {}), **({"device_jpeg": True} if device_jpeg else {}),
+          **({"device_decode": True} if device_decode else {}))
 
 
 @app.command()

@@ -32,5 +32,9 @@ struct Args {
 // every kernel of one image, in order, on `st`; nothing synchronises
 hipError_t launch_encode(const Args& a, hipStream_t st);
 
+// the exclusive scan the encoder's passes are joined by, for the decoder too (kernels_jpegdec.hip): out[i] = the sum of in[0 .. i),
+// out[n] = the total; sums: one word per kScanChunk entries
+hipError_t launch_scan(const uint32_t* in, uint64_t n, uint64_t* sums, uint64_t* out, hipStream_t st);
+
 }  // namespace jpeg
 }  // namespace v1c

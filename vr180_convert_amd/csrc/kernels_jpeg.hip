@@ -325,9 +325,7 @@ __global__ __launch_bounds__(256) void k_jpeg_place(Args a, uint64_t pieces)
     }
 }
 
-namespace {
-
-hipError_t scan(const uint32_t* in, uint64_t n, uint64_t* sums, uint64_t* out, hipStream_t st)
+hipError_t launch_scan(const uint32_t* in, uint64_t n, uint64_t* sums, uint64_t* out, hipStream_t st)
 {
     const uint32_t nchunks = (uint32_t)((n + kScanChunk - 1) / kScanChunk);
     hipLaunchKernelGGL(k_jpeg_scan_sum, dim3(nchunks), dim3(256), 0, st, in, n, sums);
@@ -335,8 +333,6 @@ hipError_t scan(const uint32_t* in, uint64_t n, uint64_t* sums, uint64_t* out, h
     hipLaunchKernelGGL(k_jpeg_scan_apply, dim3(nchunks), dim3(256), 0, st, in, n, (const uint64_t*)sums, out);
     return hipGetLastError();
 }
-
-}  // namespace
 
 hipError_t launch_encode(const Args& a, hipStream_t st)
 {
@@ -347,16 +343,16 @@ hipError_t launch_encode(const Args& a, hipStream_t st)
     const dim3 per_block((g.nblocks + 255) / 256), per_piece((uint32_t)((pieces + 255) / 256));
     hipLaunchKernelGGL(k_jpeg_transform, dim3((g.nblocks + 31) / 32), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_jpeg_size, per_block, dim3(256), 0, st, a);
-    hipError_t e = scan(a.bits, g.nblocks, a.sums, a.bitoff, st);
+    hipError_t e = launch_scan(a.bits, g.nblocks, a.sums, a.bitoff, st);
     if (e != hipSuccess)
         return e;
     hipLaunchKernelGGL(k_jpeg_interval_bytes, dim3((g.nint + 255) / 256), dim3(256), 0, st, a);
-    e = scan(a.ibytes, g.nint, a.sums, a.ioff, st);
+    e = launch_scan(a.ibytes, g.nint, a.sums, a.ioff, st);
     if (e != hipSuccess)
         return e;
     hipLaunchKernelGGL(k_jpeg_pack, per_block, dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_jpeg_count, per_piece, dim3(256), 0, st, a, pieces);
-    e = scan(a.ffcnt, pieces, a.sums, a.ffoff, st);
+    e = launch_scan(a.ffcnt, pieces, a.sums, a.ffoff, st);
     if (e != hipSuccess)
         return e;
     hipLaunchKernelGGL(k_jpeg_place, per_piece, dim3(256), 0, st, a, pieces);

@@ -675,6 +675,14 @@ def _to_device(img: Any, dev: torch.device) -> torch.Tensor:
     return torch.from_numpy(a).to(dev, non_blocking=False)
 
 
+def _decode_on_device(items: Sequence[Any], device: Any) -> list:
+    """``device_decode=True``: jpeg_decode_device.read_inputs -- ``.jpg`` / ``.jpeg`` paths decoded on the device, everything else and
+    files the device decoder does not take left for ``_io.imread``"""
+    from . import jpeg_decode_device
+
+    return jpeg_decode_device.read_inputs(items, device=device)
+
+
 def apply(
     transformer: TransformerBase,
     *,
@@ -688,18 +696,29 @@ def apply(
     device: Any = None,
     device_png: bool = False,
     device_jpeg: bool = False,
+    device_decode: bool = False,
 ) -> Sequence[NDArray[np.uint8]]:
     """Apply transformer to images (reference remapper.py:324-403).
 
     Returns one ``(size_output[1], size_output[0], C)`` array per input, of the input's pixel type
     (uint8, uint16 or float32; CUDA tensors in -> CUDA tensors out).  One map is shared by all
     images and, like the reference, takes its geometry from ``images[0]``; images of different
-    pixel types are remapped by one plan per type."""
+    pixel types are remapped by one plan per type.
+
+    ``device_decode=True``: ``.jpg`` / ``.jpeg`` inputs are decoded on the device (jpeg_decode_device.py) and take the device-resident
+    route -- with anything that came from the host reader uploaded to join them --, so the results are CUDA tensors; files outside the
+    device decoder's scope are read by the host as before."""
     in_paths_ = [in_paths] if isinstance(in_paths, (str, Path, np.ndarray, torch.Tensor)) else in_paths
     out_paths_ = [out_paths] if isinstance(out_paths, (str, Path)) else out_paths
     del in_paths, out_paths
 
+    if device_decode:
+        in_paths_ = _decode_on_device(list(in_paths_), device)
     images = _io.imread_many(list(in_paths_))
+    if device_decode:
+        decoded = next((im for im in images if isinstance(im, torch.Tensor) and im.is_cuda), None)
+        if decoded is not None:
+            images = [_to_device(im, decoded.device) for im in images]
     radius_ = get_radius_smart(radius, images)
     on_device = all(isinstance(im, torch.Tensor) and im.is_cuda for im in images)
     dev = images[0].device if on_device else _device(device)
@@ -960,6 +979,7 @@ def apply_lr(
     device: Any = None,
     device_png: bool = False,
     device_jpeg: bool = False,
+    device_decode: bool = False,
 ) -> None:
     """Apply transformer to a pair of images and save them side by side (reference
     remapper.py:406-520).  ``left_path == right_path`` means one file holding both eyes.
@@ -967,7 +987,17 @@ def apply_lr(
     ``device_png=True``: a ``.png`` ``out_path`` of a uint8 / uint16 side-by-side result is deflated on the device
     (png_device.imwrite_tensor) and the raw result is not copied to the host; ``merge=True`` and other formats take the host route.
     ``device_jpeg=True``: the same for a ``.jpg`` / ``.jpeg`` ``out_path`` of a uint8 result (jpeg_device.imwrite_jpeg_tensor:
-    quality 95, 4:2:0, as the host writer)."""
+    quality 95, 4:2:0, as the host writer).
+    ``device_decode=True``: ``.jpg`` / ``.jpeg`` inputs are decoded on the device (jpeg_decode_device.py) and only their bytes are
+    uploaded; one file holding both eyes is decoded once and the halves are views of it.  Files outside the device decoder's scope
+    are read by the host as before."""
+    if device_decode:
+        if isinstance(left_path, (str, Path)) and isinstance(right_path, (str, Path)) and left_path == right_path:
+            both = _decode_on_device([left_path], device)[0]
+            if isinstance(both, torch.Tensor):
+                left_path, right_path = both[:, : both.shape[1] // 2], both[:, both.shape[1] // 2 :]
+        else:
+            left_path, right_path = _decode_on_device([left_path, right_path], device)
     if isinstance(left_path, (str, Path)) and isinstance(right_path, (str, Path)) and left_path == right_path:
         image = _io.imread(left_path)
         left_path = image[:, : image.shape[1] // 2]
