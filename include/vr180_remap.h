@@ -455,6 +455,23 @@ int v1c_jpeg_decode_info(const uint8_t* file, uint64_t size, v1c_jpeg_info* info
 int v1c_jpeg_decode(int device, void* stream, const uint8_t* file, uint64_t size, void* out, int64_t pitch, int out_cn,
                     uint32_t subseq_bits, v1c_jpeg_decode_report* report);
 
+/* v1c_jpeg_decode of n files in shared kernel launches and shared synchronisation rounds: file i of sizes[i] bytes into outs[i] with
+ * pitches[i] and out_cns[i].  The pixels, reports[i].segments, .subsequences and .rounds are the single call's, file by file; the call
+ * SYNCHRONISES the stream once per round of its SLOWEST file (not once per round of every file) and once for the verdict, per chunk.
+ * All files are parsed on the host first.  status[i] is what v1c_jpeg_decode would have returned for the file: V1C_E_INVALID (NULL
+ * pointer, out_cn, pitch), V1C_E_UNSUPPORTED or V1C_E_CORRUPT from the parse with reports[i].error_pos the byte -- such a file is left
+ * out and the others are decoded -- or V1C_E_CORRUPT from the last pass with error_pos the bit: that file has no pixel stage, so its
+ * image's content is unspecified (whatever the buffer held), and every other file's image is exactly its own.
+ * max_workspace_bytes: the files are taken in order into chunks whose summed device workspace (about 200 bytes per 8 x 8 block of a
+ * file, plus its scan twice) stays within it; 0: 1 GiB; a file above it is a chunk of its own.  Chunks run one after another on the
+ * stream, each with one stream-ordered allocation; reports[i].reserved is the file's chunk and *batch_rounds (may be NULL) the round
+ * launches of all chunks together: within a chunk the largest of its files' rounds.
+ * Returns V1C_OK when it ran (n == 0: at once), V1C_E_INVALID for n < 0, NULL arrays or subseq_bits, V1C_E_UNSUPPORTED under stream
+ * capture (before anything is done), V1C_E_NODEVICE / V1C_E_HIP as the single call; then status[] and the images are unspecified.   */
+int v1c_jpeg_decode_batch(int device, void* stream, int n, const uint8_t* const* files, const uint64_t* sizes, void* const* outs,
+                          const int64_t* pitches, const int* out_cns, uint32_t subseq_bits, uint64_t max_workspace_bytes, int* status,
+                          v1c_jpeg_decode_report* reports, uint32_t* batch_rounds);
+
 #ifdef __cplusplus
 }
 #endif

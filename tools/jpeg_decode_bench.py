@@ -7,12 +7,18 @@ For every file the host-only parse is timed by itself (it is part of every call)
 clock, the synchronisation rounds the call took and the subsequences it ran over; Pillow's decode and the upload three times.  One
 JSON line per (file, subseq_bits); ``--out`` appends them to a file.
 
+``--batch N [N ...]``: instead, for every file and N, a batch of N copies through ``decode_jpeg_tensors`` against N single
+``decode_jpeg_tensor`` calls in the same process, the two alternating run by run; one JSON line per (file, N) with the times, the
+rounds of both and whether the tensors are equal.
+
     python tools/jpeg_decode_bench.py --subseq-bits 512 1024 2048 4096 --out profiles/jpeg_decode/bench.jsonl
+    python tools/jpeg_decode_bench.py --batch 2 16 64 --out profiles/jpeg_decode_batch/bench.jsonl
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/jpeg_decode_bench.py --runs 2 --device-only     (per-kernel times)
 """
 from __future__ import annotations
 
 import argparse
+import collections
 import io
 import json
 import sys
@@ -37,6 +43,65 @@ def default_files() -> dict:
     return {"docs_2048": (ROOT / "tests" / "golden" / "ref_docs" / "test.jpg").read_bytes(), "sphere_4096_q95_420": b.getvalue()}
 
 
+def _timed(fn) -> tuple:
+    """(result, milliseconds between two device events, milliseconds on the host clock until the second event has passed)"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    e0.record()
+    out = fn()
+    e1.record()
+    e1.synchronize()
+    return out, e0.elapsed_time(e1), 1e3 * (time.perf_counter() - t0)
+
+
+def _spread(v: list) -> list:
+    v = sorted(v)
+    return [round(v[0], 3), round(v[len(v) // 2], 3), round(v[-1], 3)]
+
+
+def bench_batches(V, files: dict, sizes: list, subseq_bits: list, runs: int, only: set, out_path) -> None:
+    for name, data in files.items():
+        for n in sizes:
+            if only and f"{name}:{n}" not in only:
+                continue
+            for S in subseq_bits:
+                kw = {} if S == 0 else {"subseq_bits": S}
+                items = [data] * n
+                got = V.decode_jpeg_tensors(items, **kw)  # warm-up of both: code objects, the staging buffer, the memory pool
+                rep = V.last_batch_report()
+                one = V.decode_jpeg_tensor(data, **kw)
+                single_rounds = V.last_decode_report()["rounds"]
+                equal = all(torch.equal(g, one) for g in got)
+                del got
+                torch.cuda.synchronize()
+                # Rotation: every run's tensors stay alive until more than twice the 256 MB Infinity Cache has been written since, so no
+                # run stores into lines the cache still holds from the run before (the inputs are host bytes, staged anew every call).
+                per_run = n * one.numel()
+                held = collections.deque(maxlen=max(1, -(-(2 * 256 << 20) // per_run)))
+                batch, loop = [], []
+                for _ in range(runs):  # (alternating, so that a drift of the clocks meets both alike)
+                    r, ev, host = _timed(lambda: V.decode_jpeg_tensors(items, **kw))
+                    batch.append((ev, host))
+                    held.append(r)
+                    r, ev, host = _timed(lambda: [V.decode_jpeg_tensor(d, **kw) for d in items])
+                    loop.append((ev, host))
+                    held.append(r)
+                held.clear()
+                line = {"file": name, "bytes": len(data), "shape": list(one.shape), "subseq_bits": S, "batch": n, "runs": runs,
+                        "batch_rounds": rep["batch_rounds"], "chunks": rep["chunks"], "loop_rounds": single_rounds * n,
+                        "equal_to_single": bool(equal),
+                        "batch_events_ms_min_median_max": _spread([b[0] for b in batch]), "batch_host_ms_min_median_max": _spread([b[1] for b in batch]),
+                        "loop_events_ms_min_median_max": _spread([b[0] for b in loop]), "loop_host_ms_min_median_max": _spread([b[1] for b in loop])}
+                line["loop_over_batch_median_host"] = round(line["loop_host_ms_min_median_max"][1] / line["batch_host_ms_min_median_max"][1], 3)
+                line["loop_over_batch_median_events"] = round(line["loop_events_ms_min_median_max"][1] / line["batch_events_ms_min_median_max"][1], 3)
+                text = json.dumps(line)
+                print(text, flush=True)
+                if out_path:
+                    Path(out_path).parent.mkdir(parents=True, exist_ok=True)
+                    with open(out_path, "a") as f:
+                        f.write(text + "\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("files", nargs="*", help="JPEG files (default: the docs image and a 4096 x 4096 sphere scene)")
@@ -44,6 +109,8 @@ def main() -> None:
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--device-only", action="store_true", help="skip the host path (profiler runs)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--batch", type=int, nargs="+", default=None, help="batch sizes: N copies in one decode_jpeg_tensors call against N single calls")
+    ap.add_argument("--only", nargs="*", default=[], help="with --batch: only these file:N pairs (docs_2048:64 ...)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("jpeg_decode_bench needs the MI355X")
@@ -53,6 +120,9 @@ def main() -> None:
 
     dev = torch.device("cuda", 0)
     files = {Path(f).name: Path(f).read_bytes() for f in a.files} if a.files else default_files()
+    if a.batch:
+        bench_batches(V, files, a.batch, a.subseq_bits, a.runs, set(a.only), a.out)
+        return
     for name, data in files.items():
         host = []
         ref = None

@@ -20,7 +20,8 @@ from .remapper import (anaglyph_tensors, apply, apply_lr, apply_lr_tensors, auto
 from .features import detect, match, match_points_device
 from .png_device import encode_png_tensor, imwrite_tensor
 from .jpeg_device import encode_jpeg_tensor, imwrite_jpeg_tensor
-from .jpeg_decode_device import decode_jpeg_tensor, imread_tensor, last_decode_report
+from .jpeg_decode_device import (decode_jpeg_tensor, decode_jpeg_tensors, imread_tensor, imread_tensors, last_batch_report,
+                                 last_decode_report)
 from .sharding import remap_sharded
 
 __all__ = [
@@ -59,4 +60,8 @@ __all__ = [
     "decode_jpeg_tensor",
     "imread_tensor",
     "last_decode_report",
+    # ... a list of them in shared launches and rounds (device_decode="batch" / --device-decode-batch)
+    "decode_jpeg_tensors",
+    "imread_tensors",
+    "last_batch_report",
 ]

@@ -218,6 +218,8 @@ def lr(
                                                                      "4:2:0); other formats and --merge are written by the host")] = False,
     device_decode: Annotated[bool, typer.Option("--device-decode", help="Decode .jpg / .jpeg inputs on the GPU (baseline JPEG; other "
                                                                          "files are read by the host)")] = False,
+    device_decode_batch: Annotated[bool, typer.Option("--device-decode-batch", help="As --device-decode, with all the files decoded in one "
+                                                                                     "batch that shares its kernel launches")] = False,
 ) -> None:
     """Remap a pair of fisheye images to a pair of SBS equirectangular images."""
     from .remapper import apply_lr
@@ -241,11 +243,11 @@ def lr(
         LOG.warning("--savematch ignored: it draws the feature matches of --automatch fm, and there are none without it")
     left_in: Any = left_path
     right_in: Any = right_path
-    if device_decode and automatch.startswith("devfm") and left_path != right_path:
+    if (device_decode or device_decode_batch) and automatch.startswith("devfm") and left_path != right_path:
         # decoded once, here: the matcher and apply_lr both take the tensors (apply_lr passes what is no path through)
         from . import jpeg_decode_device
 
-        left_in, right_in = jpeg_decode_device.read_inputs([left_path, right_path])
+        left_in, right_in = jpeg_decode_device.read_inputs([left_path, right_path], **({"batch": True} if device_decode_batch else {}))
     if automatch != "":
         match_image = out.with_suffix(f".match{out.suffix}") if savematch else None  # cli.py:362-365
         chain = calibrated_pair(chain, automatch, left_in, right_in, radius_, match_image)
@@ -253,7 +255,7 @@ def lr(
     apply_lr(chain, left_path=left_in, right_path=right_in, out_path=out, radius=radius_, size_output=parse_size(size),
              interpolation=interp, boarder_mode=border, boarder_value=border_value, merge=merge,
              **({"device_png": True} if device_png else {}), **({"device_jpeg": True} if device_jpeg else {}),
-             **({"device_decode": True} if device_decode else {}))
+             **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}))
 
 
 @app.command()
@@ -272,6 +274,8 @@ def s(
                                                                      "4:2:0); other formats are written by the host")] = False,
     device_decode: Annotated[bool, typer.Option("--device-decode", help="Decode .jpg / .jpeg inputs on the GPU (baseline JPEG; other "
                                                                          "files are read by the host)")] = False,
+    device_decode_batch: Annotated[bool, typer.Option("--device-decode-batch", help="As --device-decode, with all the files decoded in one "
+                                                                                     "batch that shares its kernel launches")] = False,
 ) -> None:
     """Remap fisheye images to equirectangular images (one shared map for all of them)."""
     from .remapper import apply
@@ -288,7 +292,7 @@ def s(
           size_output=parse_size(size), interpolation=_flag(interpolation, _INTERPOLATIONS, "inter_", "interpolation"),
           boarder_mode=_flag(boarder_mode, _BORDERS, "border_", "border mode"), boarder_value=boarder_value,
           **({"device_png": True} if device_png else {}), **({"device_jpeg": True} if device_jpeg else {}),
-          **({"device_decode": True} if device_decode else {}))
+          **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}))
 
 
 @app.command()

@@ -1,5 +1,6 @@
 // jpegdec.hip -- host side of the JPEG decoding entry points of the C ABI (v1c_jpeg_decode*, include/vr180_remap.h): the parse, the
-// upload from the page-locked staging buffer, the chain of kernels and the rounds of the synchronisation, whose flag the host reads.
+// upload from the page-locked staging buffer, the chain of kernels and the rounds of the synchronisation, whose flag the host reads;
+// and the same for a batch of files in shared launches and rounds (v1c_jpeg_decode_batch).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,11 +37,6 @@ struct DeviceGuard {
             (void)hipSetDevice(prev);
     }
 };
-
-size_t align256(size_t n)
-{
-    return (n + 255) & ~(size_t)255;
-}
 
 // the stream-ordered workspace of one call, released on every way out
 struct Workspace {
@@ -137,26 +133,12 @@ extern "C" int v1c_jpeg_decode(int device, void* stream, const uint8_t* file, ui
         return set_error(V1C_E_UNSUPPORTED, "v1c_jpeg_decode: the host reads a flag between the rounds, so the call cannot be captured into a graph");
 
     const std::vector<uint32_t> subfirst = sub_first(ps, S);
-    const uint32_t nseg = g.nseg, nsub = subfirst.back(), nu = ps.segoff.back();
-    const uint32_t scan_len = (uint32_t)ps.scan_len, pieces = (scan_len + kPiece - 1) / kPiece;
+    const uint32_t nseg = g.nseg, nsub = subfirst.back();
     if (report)
         report->segments = nseg, report->subsequences = nsub;
-
-    // what is uploaded, back to back in the staging buffer and in the workspace: tables, segment offsets, first subsequences, the scan
-    const size_t o_tab = 0, o_segoff = o_tab + align256(sizeof(Tables)), o_subfirst = o_segoff + align256(((size_t)nseg + 1) * 4);
-    const size_t o_scan = o_subfirst + align256(((size_t)nseg + 1) * 4), up_bytes = o_scan + align256(((size_t)pieces + 1) * kPiece);
-    // ... and what the kernels make
-    const uint64_t nmax = std::max<uint64_t>(std::max<uint64_t>(pieces, nsub), g.nblocks);
-    const size_t o_flags = up_bytes, o_drop = o_flags + 256, o_dropoff = o_drop + align256((size_t)pieces * 4);
-    const size_t o_u = o_dropoff + align256(((size_t)pieces + 1) * 8), u_bytes = align256((size_t)nu + 16);
-    const size_t o_exit0 = o_u + u_bytes, o_exit1 = o_exit0 + align256((size_t)nsub * 8), o_last = o_exit1 + align256((size_t)nsub * 8);
-    const size_t o_count = o_last + align256((size_t)nsub * 8), o_first = o_count + align256((size_t)nsub * 4);
-    const size_t o_coef = o_first + align256(((size_t)nsub + 1) * 8), coef_bytes = align256((size_t)g.nblocks * 128);
-    const size_t o_dcd = o_coef + coef_bytes, o_dcoff = o_dcd + align256((size_t)g.nblocks * 4);
-    const size_t o_sums = o_dcoff + align256(((size_t)g.nblocks + 1) * 8);
-    const size_t o_p0 = o_sums + align256((nmax / jpeg::kScanChunk + 2) * 8);
-    const size_t p0_bytes = align256((size_t)plane_pitch(g, 0) * plane_rows(g, 0)), pc_bytes = align256((size_t)plane_pitch(g, 1) * plane_rows(g, 1));
-    const size_t bytes = o_p0 + p0_bytes + (g.nc == 3 ? 2 * pc_bytes : 0);
+    // the upload (tables, segment offsets, first subsequences, the scan) and behind it what the kernels make
+    const Layout l = layout_of(ps, nsub);
+    const size_t up_bytes = l.up_bytes, u_bytes = l.u_bytes, coef_bytes = l.coef_bytes;
 
     Staging& sg = g_staging[device];
     std::lock_guard<std::mutex> lock(sg.mu);
@@ -164,40 +146,14 @@ extern "C" int v1c_jpeg_decode(int device, void* stream, const uint8_t* file, ui
     if (!stage)
         return set_error(V1C_E_HIP, "v1c_jpeg_decode: hipHostMalloc of the staging buffer failed");
     std::memset(stage, 0, up_bytes);
-    std::memcpy(stage + o_tab, &ps.tab, sizeof(Tables));
-    std::memcpy(stage + o_segoff, ps.segoff.data(), ((size_t)nseg + 1) * 4);
-    std::memcpy(stage + o_subfirst, subfirst.data(), ((size_t)nseg + 1) * 4);
-    std::memcpy(stage + o_scan, file + ps.scan_start, (size_t)scan_len + 2);  // (the parse saw the two bytes of the marker behind the scan)
+    stage_file(stage, ps, l, subfirst, file);
     volatile uint32_t* back = (volatile uint32_t*)(stage + up_bytes);        // what comes back: a round's flag, the verdict
 
     Workspace ws(st);
-    hipError_t e = hipMallocAsync((void**)&ws.p, bytes, st);
+    hipError_t e = hipMallocAsync((void**)&ws.p, l.bytes, st);
     if (e != hipSuccess)
         return set_error(V1C_E_HIP, std::string("v1c_jpeg_decode: hipMallocAsync: ") + hipGetErrorString(e));
-    Args a{};
-    a.g = g;
-    a.tab = (const Tables*)(ws.p + o_tab);
-    a.scan = ws.p + o_scan;
-    a.scan_len = scan_len, a.pieces = pieces;
-    a.drop = (uint32_t*)(ws.p + o_drop);
-    a.dropoff = (uint64_t*)(ws.p + o_dropoff);
-    a.u = (uint32_t*)(ws.p + o_u);
-    a.segoff = (const uint32_t*)(ws.p + o_segoff);
-    a.subfirst = (const uint32_t*)(ws.p + o_subfirst);
-    a.nsub = nsub, a.S = S;
-    a.exit[0] = (State*)(ws.p + o_exit0), a.exit[1] = (State*)(ws.p + o_exit1);
-    a.last = (State*)(ws.p + o_last);
-    a.count = (uint32_t*)(ws.p + o_count);
-    a.first = (uint64_t*)(ws.p + o_first);
-    a.flags = (uint32_t*)(ws.p + o_flags);
-    a.coef = (int16_t*)(ws.p + o_coef);
-    a.dcd = (uint32_t*)(ws.p + o_dcd);
-    a.dcoff = (uint64_t*)(ws.p + o_dcoff);
-    a.sums = (uint64_t*)(ws.p + o_sums);
-    a.plane[0] = ws.p + o_p0;
-    a.plane[1] = g.nc == 3 ? ws.p + o_p0 + p0_bytes : nullptr;
-    a.plane[2] = g.nc == 3 ? ws.p + o_p0 + p0_bytes + pc_bytes : nullptr;
-    a.out = (uint8_t*)out, a.pitch = pitch, a.out_cn = (uint32_t)out_cn;
+    const Args a = args_of(ps, l, nsub, S, ws.p, ws.p + up_bytes, (uint32_t*)(ws.p + up_bytes + l.o_flags), out, pitch, out_cn);
 
     e = hipMemcpyAsync(ws.p, stage, up_bytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
@@ -244,5 +200,209 @@ extern "C" int v1c_jpeg_decode(int device, void* stream, const uint8_t* file, ui
     e = launch_pixels(a, st);
     if (e != hipSuccess)
         return set_error(V1C_E_HIP, std::string("v1c_jpeg_decode (pixels): ") + hipGetErrorString(e));
+    return V1C_OK;
+}
+
+namespace {
+
+// one file of a batch that the parse accepted
+struct BatchFile {
+    int index;  // in the caller's arrays
+    Parsed ps;
+    std::vector<uint32_t> subfirst;
+    uint32_t nsub = 0, rounds = 0;
+    Layout l{};
+    uint64_t groups[kWorkLists] = {};
+};
+
+uint64_t groups_of(uint64_t n, uint32_t per)
+{
+    return (n + per - 1) / per;
+}
+
+// One chunk: files [lo, hi) of `files` in one allocation, one upload and shared launches.  status / reports: the caller's arrays.
+// Returns a HIP error, and the chunk's round launches in *rounds.
+hipError_t decode_chunk(Staging& sg, hipStream_t st, std::vector<BatchFile>& files, size_t lo, size_t hi, const uint8_t* const* data,
+                        void* const* outs, const int64_t* pitches, const int* out_cns, uint32_t S, int* status,
+                        v1c_jpeg_decode_report* reports, uint32_t* rounds)
+{
+    const uint32_t n = (uint32_t)(hi - lo);
+    // the chunk's head -- Args, work lists, last rounds, flags --, then every file's upload, then every file's work
+    const size_t o_args = 0, o_first = o_args + align256((size_t)n * sizeof(Args)), o_rounds = o_first + align256((size_t)kWorkLists * (n + 1) * 4);
+    const size_t o_flags = o_rounds + align256((size_t)n * 4), flag_bytes = (size_t)n * kFlagWords * 4;
+    std::vector<size_t> o_up(n), o_work(n);
+    size_t at = o_flags + align256(flag_bytes);
+    for (uint32_t f = 0; f < n; f++)
+        o_up[f] = at, at += files[lo + f].l.up_bytes;
+    const size_t up_bytes = at;
+    for (uint32_t f = 0; f < n; f++)
+        o_work[f] = at, at += files[lo + f].l.work_bytes;
+    const size_t bytes = at;
+
+    uint8_t* stage = staging(sg, up_bytes + flag_bytes + 64);
+    if (!stage)
+        return hipErrorOutOfMemory;
+    std::memset(stage, 0, up_bytes);
+    Args* args = (Args*)(stage + o_args);
+    uint32_t *first = (uint32_t*)(stage + o_first), *last_round = (uint32_t*)(stage + o_rounds), *flags = (uint32_t*)(stage + o_flags);
+    volatile uint32_t* back = (volatile uint32_t*)(stage + up_bytes);  // what comes back: all the files' flags
+
+    Workspace ws(st);
+    hipError_t e = hipMallocAsync((void**)&ws.p, bytes, st);
+    if (e != hipSuccess)
+        return e;
+    uint32_t most = 0;
+    for (uint32_t f = 0; f < n; f++) {
+        const BatchFile& bf = files[lo + f];
+        args[f] = args_of(bf.ps, bf.l, bf.nsub, S, ws.p + o_up[f], ws.p + o_work[f], (uint32_t*)(ws.p + o_flags) + (size_t)f * kFlagWords,
+                          outs[bf.index], pitches[bf.index], out_cns[bf.index]);
+        stage_file(stage + o_up[f], bf.ps, bf.l, bf.subfirst, data[bf.index]);
+        flags[f * kFlagWords + kErrSlot] = kNoError;
+        for (int l = 0; l < kWorkLists; l++)
+            first[(size_t)l * (n + 1) + f + 1] = first[(size_t)l * (n + 1) + f] + (uint32_t)bf.groups[l];
+        most = std::max(most, bf.nsub);
+    }
+    std::vector<int> skip(n, 0);
+    const Batch b{(const Args*)(ws.p + o_args), (const uint32_t*)(ws.p + o_first), (const uint32_t*)(ws.p + o_rounds), n};
+    const BatchHost h{args, first, skip.data()};
+
+    e = hipMemcpyAsync(ws.p, stage, up_bytes, hipMemcpyHostToDevice, st);
+    for (uint32_t f = 0; f < n && e == hipSuccess; f++) {
+        e = hipMemsetAsync(args[f].u, 0, files[lo + f].l.u_bytes, st);
+        if (e == hipSuccess)
+            e = hipMemsetAsync(args[f].coef, 0, files[lo + f].l.coef_bytes, st);
+    }
+    if (e == hipSuccess)
+        e = launch_unstuff_batch(b, h, st);
+    if (e == hipSuccess)
+        e = launch_sync_init_batch(b, h, st);
+    // the rounds: a file is done at its first quiet round or at its own bound, the chunk when all its files are
+    uint32_t r = 0, open = n;
+    while (e == hipSuccess && open) {
+        r++;
+        e = launch_sync_round_batch(b, h, r, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync((void*)back, ws.p + o_flags, flag_bytes, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(st);
+        if (e != hipSuccess)
+            break;
+        for (uint32_t f = 0; f < n; f++) {
+            BatchFile& bf = files[lo + f];
+            if (!bf.rounds && (back[f * kFlagWords + r % kRoundSlots] == 0 || r > bf.nsub))
+                bf.rounds = r, open--;
+        }
+        if (r > most)
+            break;
+    }
+    *rounds = r;
+    for (uint32_t f = 0; f < n; f++)
+        last_round[f] = reports[files[lo + f].index].rounds = files[lo + f].rounds;
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(ws.p + o_rounds, last_round, (size_t)n * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = launch_write_batch(b, h, st);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync((void*)back, ws.p + o_flags, flag_bytes, hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);  // (also on an error above: nothing of this chunk reads the staging buffer after this)
+    if (e == hipSuccess)
+        e = es;
+    if (e != hipSuccess)
+        return e;
+    for (uint32_t f = 0; f < n; f++) {
+        const uint32_t err = back[f * kFlagWords + kErrSlot];
+        if (err != kNoError) {
+            skip[f] = 1;
+            status[files[lo + f].index] = V1C_E_CORRUPT;
+            reports[files[lo + f].index].error_pos = err;
+        }
+    }
+    return launch_pixels_batch(b, h, st);
+}
+
+}  // namespace
+
+extern "C" int v1c_jpeg_decode_batch(int device, void* stream, int n, const uint8_t* const* files, const uint64_t* sizes, void* const* outs,
+                                     const int64_t* pitches, const int* out_cns, uint32_t subseq_bits, uint64_t max_workspace_bytes,
+                                     int* status, v1c_jpeg_decode_report* reports, uint32_t* batch_rounds)
+{
+    if (batch_rounds)
+        *batch_rounds = 0;
+    if (n < 0)
+        return set_error(V1C_E_INVALID, "v1c_jpeg_decode_batch: n is negative");
+    if (n == 0)
+        return V1C_OK;
+    if (!files || !sizes || !outs || !pitches || !out_cns || !status || !reports)
+        return set_error(V1C_E_INVALID, "v1c_jpeg_decode_batch: NULL pointer");
+    const uint32_t S = subseq_bits ? subseq_bits : kDefaultSubseqBits;
+    if (S % 32 || S < 256 || S > (1u << 24))
+        return set_error(V1C_E_INVALID, "v1c_jpeg_decode_batch: subseq_bits must be a multiple of 32 from 256 to 2^24, or 0");
+    // (device and capture first: under capture nothing is done, not even a status written)
+    if (device < 0 || device >= kMaxDevices)
+        return set_error(V1C_E_NODEVICE, "v1c_jpeg_decode_batch: no such device");
+    DeviceGuard dg(device);
+    if (!dg.ok)
+        return set_error(V1C_E_NODEVICE, "hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+        return set_error(V1C_E_UNSUPPORTED, "v1c_jpeg_decode_batch: the host reads a flag between the rounds, so the call cannot be captured into a graph");
+    std::memset(reports, 0, sizeof(*reports) * (size_t)n);
+
+    // every file's arguments and parse, before the device is touched: a file refused here has its status and is left out
+    std::vector<BatchFile> good;
+    good.reserve((size_t)n);
+    for (int i = 0; i < n; i++) {
+        status[i] = V1C_OK;
+        if (!files[i] || !outs[i] || (out_cns[i] != 1 && out_cns[i] != 3)) {
+            status[i] = V1C_E_INVALID;
+            continue;
+        }
+        good.emplace_back();
+        BatchFile& bf = good.back();
+        const ParseResult pr = parse(files[i], sizes[i], bf.ps);
+        const Geom& g = bf.ps.g;
+        if (pr != kParsed) {
+            status[i] = pr == kUnsupported ? V1C_E_UNSUPPORTED : V1C_E_CORRUPT;
+            reports[i].error_pos = bf.ps.error_pos;
+        } else if ((out_cns[i] == 1 && g.nc != 1) || pitches[i] < (int64_t)g.w * out_cns[i]) {
+            status[i] = V1C_E_INVALID;
+        }
+        if (status[i] != V1C_OK) {
+            good.pop_back();
+            continue;
+        }
+        bf.index = i;
+        bf.subfirst = sub_first(bf.ps, S);
+        bf.nsub = bf.subfirst.back();
+        bf.l = layout_of(bf.ps, bf.nsub);
+        bf.groups[kByPiece] = groups_of(bf.l.pieces, 256), bf.groups[kBySub] = groups_of(bf.nsub, 256);
+        bf.groups[kByBlock] = groups_of(g.nblocks, 256), bf.groups[kByTile] = groups_of(g.nblocks, 32);
+        bf.groups[kByPixel] = groups_of((uint64_t)((g.w + 3) / 4) * g.h, 256);
+        reports[i].segments = g.nseg, reports[i].subsequences = bf.nsub;
+    }
+    if (good.empty())
+        return V1C_OK;
+
+    std::vector<uint64_t> bytes, groups;
+    for (const BatchFile& bf : good) {
+        bytes.push_back(bf.l.bytes + sizeof(Args) + 1024);  // (with the file's share of the chunk's head)
+        groups.push_back(*std::max_element(bf.groups, bf.groups + kWorkLists));
+    }
+    Staging& sg = g_staging[device];
+    std::lock_guard<std::mutex> lock(sg.mu);
+    size_t lo = 0;
+    uint32_t chunk = 0;
+    for (uint32_t hi : chunk_ends(bytes, groups, max_workspace_bytes ? max_workspace_bytes : kDefaultBatchWorkspace)) {
+        for (size_t f = lo; f < hi; f++)
+            reports[good[f].index].reserved = chunk;
+        uint32_t rounds = 0;
+        const hipError_t e = decode_chunk(sg, st, good, lo, hi, files, outs, pitches, out_cns, S, status, reports, &rounds);
+        if (batch_rounds)
+            *batch_rounds += rounds;
+        if (e != hipSuccess)
+            return set_error(V1C_E_HIP, std::string("v1c_jpeg_decode_batch (chunk ") + std::to_string(chunk) + "): " + hipGetErrorString(e));
+        lo = hi, chunk++;
+    }
     return V1C_OK;
 }

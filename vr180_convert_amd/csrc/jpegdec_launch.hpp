@@ -5,7 +5,9 @@
 #include <stdint.h>
 
 #include "jpeg_launch.hpp"
+#include "jpegdec_batch.hpp"
 #include "jpegdec_core.hpp"
+#include "jpegdec_host.hpp"
 
 namespace v1c {
 namespace jpegdec {
@@ -39,6 +41,89 @@ struct Args {
     uint32_t out_cn;         // 1 or 3
 };
 
+// Where the buffers of one file lie: what is uploaded (tables, segment offsets, first subsequences, the scan) back to back from the
+// upload's base, and what the kernels make back to back from the work's base, each piece aligned to 256 bytes.  The single call puts
+// the work behind the upload in one allocation; a batch puts all its files' uploads in front of all their work, so that one copy
+// brings a chunk's files to the device.
+struct Layout {
+    size_t o_tab, o_segoff, o_subfirst, o_scan, up_bytes;                                // from the upload's base
+    size_t o_flags, o_drop, o_dropoff, o_u, u_bytes, o_exit0, o_exit1, o_last, o_count;  // from the work's base
+    size_t o_first, o_coef, coef_bytes, o_dcd, o_dcoff, o_sums, o_p0, p0_bytes, pc_bytes, work_bytes;
+    size_t bytes;                                                                        // up_bytes + work_bytes
+    uint32_t pieces;
+};
+
+inline size_t align256(size_t n)
+{
+    return (n + 255) & ~(size_t)255;
+}
+
+inline Layout layout_of(const Parsed& ps, uint32_t nsub)
+{
+    const Geom& g = ps.g;
+    const size_t nseg = g.nseg;
+    Layout l{};
+    l.pieces = ((uint32_t)ps.scan_len + kPiece - 1) / kPiece;
+    const size_t pieces = l.pieces, nu = ps.segoff.back();
+    l.o_tab = 0, l.o_segoff = l.o_tab + align256(sizeof(Tables)), l.o_subfirst = l.o_segoff + align256((nseg + 1) * 4);
+    l.o_scan = l.o_subfirst + align256((nseg + 1) * 4), l.up_bytes = l.o_scan + align256((pieces + 1) * kPiece);
+    const uint64_t nmax = pieces > nsub ? (pieces > g.nblocks ? pieces : g.nblocks) : (nsub > g.nblocks ? nsub : g.nblocks);
+    l.o_flags = 0, l.o_drop = l.o_flags + 256, l.o_dropoff = l.o_drop + align256(pieces * 4);
+    l.o_u = l.o_dropoff + align256((pieces + 1) * 8), l.u_bytes = align256(nu + 16);
+    l.o_exit0 = l.o_u + l.u_bytes, l.o_exit1 = l.o_exit0 + align256((size_t)nsub * 8), l.o_last = l.o_exit1 + align256((size_t)nsub * 8);
+    l.o_count = l.o_last + align256((size_t)nsub * 8), l.o_first = l.o_count + align256((size_t)nsub * 4);
+    l.o_coef = l.o_first + align256(((size_t)nsub + 1) * 8), l.coef_bytes = align256((size_t)g.nblocks * 128);
+    l.o_dcd = l.o_coef + l.coef_bytes, l.o_dcoff = l.o_dcd + align256((size_t)g.nblocks * 4);
+    l.o_sums = l.o_dcoff + align256(((size_t)g.nblocks + 1) * 8);
+    l.o_p0 = l.o_sums + align256((nmax / jpeg::kScanChunk + 2) * 8);
+    l.p0_bytes = align256((size_t)plane_pitch(g, 0) * plane_rows(g, 0)), l.pc_bytes = align256((size_t)plane_pitch(g, 1) * plane_rows(g, 1));
+    l.work_bytes = l.o_p0 + l.p0_bytes + (g.nc == 3 ? 2 * l.pc_bytes : 0);
+    l.bytes = l.up_bytes + l.work_bytes;
+    return l;
+}
+
+// the Args of a file whose upload lies at `up` and whose work at `work` (device addresses); flags: the file's flag words
+inline Args args_of(const Parsed& ps, const Layout& l, uint32_t nsub, uint32_t S, uint8_t* up, uint8_t* work, uint32_t* flags, void* out,
+                    int64_t pitch, int out_cn)
+{
+    const Geom& g = ps.g;
+    Args a{};
+    a.g = g;
+    a.tab = (const Tables*)(up + l.o_tab);
+    a.scan = up + l.o_scan;
+    a.scan_len = (uint32_t)ps.scan_len, a.pieces = l.pieces;
+    a.drop = (uint32_t*)(work + l.o_drop);
+    a.dropoff = (uint64_t*)(work + l.o_dropoff);
+    a.u = (uint32_t*)(work + l.o_u);
+    a.segoff = (const uint32_t*)(up + l.o_segoff);
+    a.subfirst = (const uint32_t*)(up + l.o_subfirst);
+    a.nsub = nsub, a.S = S;
+    a.exit[0] = (State*)(work + l.o_exit0), a.exit[1] = (State*)(work + l.o_exit1);
+    a.last = (State*)(work + l.o_last);
+    a.count = (uint32_t*)(work + l.o_count);
+    a.first = (uint64_t*)(work + l.o_first);
+    a.flags = flags;
+    a.coef = (int16_t*)(work + l.o_coef);
+    a.dcd = (uint32_t*)(work + l.o_dcd);
+    a.dcoff = (uint64_t*)(work + l.o_dcoff);
+    a.sums = (uint64_t*)(work + l.o_sums);
+    a.plane[0] = work + l.o_p0;
+    a.plane[1] = g.nc == 3 ? work + l.o_p0 + l.p0_bytes : nullptr;
+    a.plane[2] = g.nc == 3 ? work + l.o_p0 + l.p0_bytes + l.pc_bytes : nullptr;
+    a.out = (uint8_t*)out, a.pitch = pitch, a.out_cn = (uint32_t)out_cn;
+    return a;
+}
+
+// a file's upload in host memory at `stage` (zeroed by the caller): tables, segment offsets, first subsequences, the scan
+inline void stage_file(uint8_t* stage, const Parsed& ps, const Layout& l, const std::vector<uint32_t>& subfirst, const uint8_t* file)
+{
+    const size_t nseg = ps.g.nseg;
+    std::memcpy(stage + l.o_tab, &ps.tab, sizeof(Tables));
+    std::memcpy(stage + l.o_segoff, ps.segoff.data(), (nseg + 1) * 4);
+    std::memcpy(stage + l.o_subfirst, subfirst.data(), (nseg + 1) * 4);
+    std::memcpy(stage + l.o_scan, file + ps.scan_start, (size_t)ps.scan_len + 2);  // (the parse saw the two bytes of the marker behind the scan)
+}
+
 // unstuffing: drop counts, their scan, and the compaction to a.u.  Nothing synchronises.
 hipError_t launch_unstuff(const Args& a, hipStream_t st);
 // exit[0] = the grid states, last = none
@@ -49,6 +134,31 @@ hipError_t launch_sync_round(const Args& a, uint32_t r, hipStream_t st);
 hipError_t launch_write(const Args& a, uint32_t r, hipStream_t st);
 // DC scan, inverse DCT into the planes, upsampling and colour conversion into a.out
 hipError_t launch_pixels(const Args& a, hipStream_t st);
+
+// ---- a batch: a chunk of n files in shared launches (kernels_jpegdec_batch.hip) --------------------------------
+struct Batch {
+    const Args* args;        // n, on the device; every file's flags are kFlagWords words (jpegdec_batch.hpp)
+    const uint32_t* first;   // kWorkLists x (n + 1): the work lists
+    const uint32_t* rounds;  // n: every file's last round, whose parity the last pass reads the exit states by
+    uint32_t n;
+};
+
+// What the host knows of the chunk's files, for the grids and for the scans, which stay one set of launches per file: they lie outside
+// the round loop, and nothing synchronises between them.
+struct BatchHost {
+    const Args* args;       // n, on the host
+    const uint32_t* first;  // kWorkLists x (n + 1), on the host: what b.first holds when the launch runs
+    const int* skip;        // n: nonzero for a file without the pixel stage
+};
+
+hipError_t launch_unstuff_batch(const Batch& b, const BatchHost& h, hipStream_t st);
+hipError_t launch_sync_init_batch(const Batch& b, const BatchHost& h, hipStream_t st);
+// round r of every file that is still moving: one launch
+hipError_t launch_sync_round_batch(const Batch& b, const BatchHost& h, uint32_t r, hipStream_t st);
+// the block-count scans and the last pass; b.rounds must have arrived
+hipError_t launch_write_batch(const Batch& b, const BatchHost& h, hipStream_t st);
+// the pixel stage; the workgroups of a file whose flags hold an error bit return at once, and h.skip spares it the DC scan
+hipError_t launch_pixels_batch(const Batch& b, const BatchHost& h, hipStream_t st);
 
 }  // namespace jpegdec
 

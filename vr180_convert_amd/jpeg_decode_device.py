@@ -32,6 +32,7 @@ class _Report(C.Structure):
 
 LOG = logging.getLogger(__name__)
 _last: dict = {}
+_last_batch: dict = {}
 
 
 class CorruptJPEG(ValueError):
@@ -95,11 +96,117 @@ def last_decode_report() -> dict:
     return dict(_last)
 
 
-def read_inputs(items: Any, *, device: Any = None) -> list:
+def _error_of(rc: int, what: str, msg: str) -> Exception:
+    """the exception ``_check`` raises for a return code, as an object"""
+    if rc == _abi.E_CORRUPT:
+        return CorruptJPEG(f"{what}: {msg}")
+    if rc == _abi.E_INVALID:
+        return ValueError(f"{what}: {msg}")
+    if rc == _abi.E_UNSUPPORTED:
+        return NotImplementedError(f"{what}: {msg}")
+    return _native.EngineError(f"{what}: {msg} (code {rc})")
+
+
+def decode_jpeg_tensors(items: Any, *, device: Any = None, channels: int = 3, subseq_bits: int | None = None,
+                        max_workspace_bytes: int | None = None, errors: str = "raise") -> list:
+    """``decode_jpeg_tensor`` of every item (bytes or paths) in ONE call of the engine (``v1c_jpeg_decode_batch``): the files share
+    their kernel launches and their synchronisation rounds, so the list costs the rounds of its slowest file and not the sum.  The
+    tensors, and what a file is refused for, are those of ``decode_jpeg_tensor`` file by file.  ``max_workspace_bytes``: the files are
+    taken in order into chunks whose device workspace stays under it (None: the engine's default; a larger file is a chunk of its
+    own).  ``errors="raise"``: after the batch ran, the first failing file's exception is raised; ``errors="return"``: every failing
+    file's exception object stands in its place in the list and the others are decoded.  ``last_batch_report()`` tells what the call
+    did; ``last_decode_report()`` is left alone."""
+    if errors not in ("raise", "return"):
+        raise ValueError('errors must be "raise" or "return"')
+    if channels not in (1, 3):
+        raise ValueError("channels must be 1 or 3")
+    S = 0 if subseq_bits is None else int(subseq_bits)
+    if S and (S % 32 or S < 256):
+        raise ValueError("subseq_bits must be a multiple of 32, at least 256")
+    items = list(items)
+    n = len(items)
+    out: list = [None] * n
+    data: list = [b""] * n
+    for i, q in enumerate(items):
+        try:
+            data[i] = _bytes_of(q)
+            h, w, nc = probe(data[i])
+            if channels == 1 and nc != 1:
+                raise ValueError("channels=1 takes a grey file")
+            out[i] = (h, w)
+        except (NotImplementedError, ValueError, OSError) as e:  # (what decode_jpeg_tensor raises before it looks for a device)
+            out[i] = e
+    live = [i for i in range(n) if not isinstance(out[i], Exception)]
+    reports: list = [None] * n
+    rounds = C.c_uint32(0)
+    chunks = 0
+    if live:
+        dev = _device(device)
+        m = len(live)
+        for i in live:
+            h, w = out[i]
+            out[i] = torch.empty((h, w) if channels == 1 else (h, w, 3), dtype=torch.uint8, device=dev)
+        files = (C.c_char_p * m)(*[data[i] for i in live])
+        sizes = (C.c_uint64 * m)(*[len(data[i]) for i in live])
+        outs = (C.c_void_p * m)(*[out[i].data_ptr() for i in live])
+        pitches = (C.c_int64 * m)(*[out[i].shape[1] * channels for i in live])
+        cns = (C.c_int * m)(*([channels] * m))
+        status = (C.c_int * m)()
+        reps = (_Report * m)()
+        budget = 0 if max_workspace_bytes is None else int(max_workspace_bytes)
+        rc = _native.lib().v1c_jpeg_decode_batch(dev.index, _stream_ptr(dev), m, files, sizes, outs, pitches, cns, S, budget, status, reps,
+                                                 C.byref(rounds))
+        _check(rc, "v1c_jpeg_decode_batch")
+        for k, i in enumerate(live):
+            reports[i] = dict(segments=reps[k].segments, subsequences=reps[k].subsequences, rounds=reps[k].rounds, path="device")
+            if status[k] != _abi.OK:
+                what = (f"the entropy-coded data is damaged at bit {reps[k].error_pos} of the unstuffed scan" if status[k] == _abi.E_CORRUPT
+                        else f"status {status[k]}")
+                out[i] = _error_of(status[k], "v1c_jpeg_decode_batch", f"file {i}: {what}")
+                reports[i] = None
+        chunks = max((reps[k].reserved + 1 for k in range(m) if reps[k].subsequences), default=0)  # (reserved: the file's chunk)
+    _last_batch.clear()
+    _last_batch.update(batch_rounds=int(rounds.value), chunks=int(chunks), files=reports)
+    if errors == "raise":
+        for o in out:
+            if isinstance(o, Exception):
+                raise o
+    return out
+
+
+def imread_tensors(paths: Any, *, device: Any = None, channels: int = 3, subseq_bits: int | None = None,
+                   max_workspace_bytes: int | None = None, errors: str = "raise") -> list:
+    """``decode_jpeg_tensors`` of files"""
+    return decode_jpeg_tensors([Path(p) for p in paths], device=device, channels=channels, subseq_bits=subseq_bits,
+                               max_workspace_bytes=max_workspace_bytes, errors=errors)
+
+
+def last_batch_report() -> dict:
+    """of the last ``decode_jpeg_tensors`` call: ``batch_rounds`` (round launches, summed over the chunks), ``chunks`` and ``files``, per
+    file the dict ``last_decode_report()`` gives after a single call, or None for a file that was not decoded"""
+    return dict(_last_batch)
+
+
+def read_inputs(items: Any, *, device: Any = None, batch: bool = False) -> list:
     """What ``device_decode=True`` does with its inputs: the ``.jpg`` / ``.jpeg`` paths among ``items`` become BGR device tensors; every
     other entry (arrays, tensors, other suffixes) is handed back as it is.  A file outside the device decoder's scope (progressive,
     ...) stays a path for the host reader; so does one that is damaged or cannot be read, with a warning, so that such a file meets
-    the host reader's behaviour as it does without the option.  Any other error is raised."""
+    the host reader's behaviour as it does without the option.  Any other error is raised.  ``batch=True`` (``device_decode="batch"``):
+    the same outcomes and log lines from one ``imread_tensors`` call over all the eligible paths."""
+    if batch:
+        items = list(items)
+        at = [i for i, q in enumerate(items) if eligible(q)]
+        got = imread_tensors([items[i] for i in at], device=device, errors="return") if at else []
+        for i, t in zip(at, got):
+            if isinstance(t, NotImplementedError):
+                LOG.info(f"{items[i]}: read on the host ({t})")
+            elif isinstance(t, (CorruptJPEG, OSError)):
+                LOG.warning(f"{items[i]}: left to the host reader ({t})")
+            elif isinstance(t, Exception):
+                raise t
+            else:
+                items[i] = t
+        return items
     out = []
     for q in items:
         if eligible(q):
@@ -118,4 +225,5 @@ def eligible(path: Any) -> bool:
     return isinstance(path, (str, Path)) and Path(path).suffix.lower() in (".jpg", ".jpeg")
 
 
-__all__ = ["decode_jpeg_tensor", "imread_tensor", "read_inputs", "last_decode_report", "eligible", "probe", "CorruptJPEG"]
+__all__ = ["decode_jpeg_tensor", "imread_tensor", "decode_jpeg_tensors", "imread_tensors", "read_inputs", "last_decode_report",
+           "last_batch_report", "eligible", "probe", "CorruptJPEG"]

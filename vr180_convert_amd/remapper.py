@@ -675,11 +675,15 @@ def _to_device(img: Any, dev: torch.device) -> torch.Tensor:
     return torch.from_numpy(a).to(dev, non_blocking=False)
 
 
-def _decode_on_device(items: Sequence[Any], device: Any) -> list:
+def _decode_on_device(items: Sequence[Any], device: Any, mode: Any = True) -> list:
     """``device_decode=True``: jpeg_decode_device.read_inputs -- ``.jpg`` / ``.jpeg`` paths decoded on the device, everything else and
-    files the device decoder does not take left for ``_io.imread``"""
+    files the device decoder does not take left for ``_io.imread``; ``device_decode="batch"``: the same through one batched decode"""
     from . import jpeg_decode_device
 
+    if isinstance(mode, str) and mode != "batch":
+        raise ValueError('device_decode must be True, False or "batch"')
+    if mode == "batch":
+        return jpeg_decode_device.read_inputs(items, device=device, batch=True)
     return jpeg_decode_device.read_inputs(items, device=device)
 
 
@@ -696,7 +700,7 @@ def apply(
     device: Any = None,
     device_png: bool = False,
     device_jpeg: bool = False,
-    device_decode: bool = False,
+    device_decode: bool | Literal["batch"] = False,
 ) -> Sequence[NDArray[np.uint8]]:
     """Apply transformer to images (reference remapper.py:324-403).
 
@@ -707,13 +711,14 @@ def apply(
 
     ``device_decode=True``: ``.jpg`` / ``.jpeg`` inputs are decoded on the device (jpeg_decode_device.py) and take the device-resident
     route -- with anything that came from the host reader uploaded to join them --, so the results are CUDA tensors; files outside the
-    device decoder's scope are read by the host as before."""
+    device decoder's scope are read by the host as before.  ``device_decode="batch"``: the same, with all the files decoded in one
+    batch that shares its launches and synchronisation rounds (jpeg_decode_device.decode_jpeg_tensors)."""
     in_paths_ = [in_paths] if isinstance(in_paths, (str, Path, np.ndarray, torch.Tensor)) else in_paths
     out_paths_ = [out_paths] if isinstance(out_paths, (str, Path)) else out_paths
     del in_paths, out_paths
 
     if device_decode:
-        in_paths_ = _decode_on_device(list(in_paths_), device)
+        in_paths_ = _decode_on_device(list(in_paths_), device, device_decode)
     images = _io.imread_many(list(in_paths_))
     if device_decode:
         decoded = next((im for im in images if isinstance(im, torch.Tensor) and im.is_cuda), None)
@@ -979,7 +984,7 @@ def apply_lr(
     device: Any = None,
     device_png: bool = False,
     device_jpeg: bool = False,
-    device_decode: bool = False,
+    device_decode: bool | Literal["batch"] = False,
 ) -> None:
     """Apply transformer to a pair of images and save them side by side (reference
     remapper.py:406-520).  ``left_path == right_path`` means one file holding both eyes.
@@ -990,14 +995,14 @@ def apply_lr(
     quality 95, 4:2:0, as the host writer).
     ``device_decode=True``: ``.jpg`` / ``.jpeg`` inputs are decoded on the device (jpeg_decode_device.py) and only their bytes are
     uploaded; one file holding both eyes is decoded once and the halves are views of it.  Files outside the device decoder's scope
-    are read by the host as before."""
+    are read by the host as before.  ``device_decode="batch"``: the same, with the two files decoded as one batch of two."""
     if device_decode:
         if isinstance(left_path, (str, Path)) and isinstance(right_path, (str, Path)) and left_path == right_path:
-            both = _decode_on_device([left_path], device)[0]
+            both = _decode_on_device([left_path], device, device_decode)[0]
             if isinstance(both, torch.Tensor):
                 left_path, right_path = both[:, : both.shape[1] // 2], both[:, both.shape[1] // 2 :]
         else:
-            left_path, right_path = _decode_on_device([left_path, right_path], device)
+            left_path, right_path = _decode_on_device([left_path, right_path], device, device_decode)
     if isinstance(left_path, (str, Path)) and isinstance(right_path, (str, Path)) and left_path == right_path:
         image = _io.imread(left_path)
         left_path = image[:, : image.shape[1] // 2]
