@@ -419,6 +419,26 @@ int64_t v1c_jpeg_header(int h, int w, int cn, int quality, int subsampling, int 
 int v1c_jpeg_encode(int device, void* stream, const void* img, int h, int w, int64_t pitch, int cn, int quality, int subsampling,
                     int restart_mcus, uint8_t* out_host, uint64_t capacity, uint64_t* size_out);
 
+/* A list of device images in shared launches: every out_host receives, byte for byte, the scan v1c_jpeg_encode writes for that image
+ * and those parameters, and `size` its size.  Size, channels, pitch, quality, subsampling and restart interval are per image.  The
+ * images of a chunk share ONE stream-ordered workspace, one upload (descriptors, work lists, one set of tables per distinct
+ * quality), one chain of kernels and TWO synchronisations: one for all sizes, one for all scans (one copy of exactly `size` bytes per
+ * image).  The list is cut into chunks whose workspaces -- about 760 bytes per 8 x 8 block -- stay within workspace_budget (0: 1 GiB);
+ * an image larger than the budget is a chunk of its own; *chunks_out (may be NULL): the chunks that ran.  All arguments of all
+ * images are checked with v1c_jpeg_encode's rules before any device call: a bad image makes the whole call V1C_E_INVALID and the
+ * message names its index; n < 0 or a NULL array are V1C_E_INVALID, n == 0 returns V1C_OK at once.  The call synchronises inside:
+ * V1C_E_UNSUPPORTED, before anything is done, while `stream` is being captured into a graph.                                      */
+typedef struct v1c_jpeg_image {       /* one image of a batch; every field as the argument of the same name of v1c_jpeg_encode */
+    const void* img;
+    int h, w;
+    int64_t pitch;
+    int cn, quality, subsampling, restart_mcus;
+    uint8_t* out_host;
+    uint64_t capacity;                /* >= v1c_jpeg_bound of this image                                                        */
+    uint64_t size;                    /* out: bytes of its scan                                                                 */
+} v1c_jpeg_image;
+int v1c_jpeg_encode_batch(int device, void* stream, int n, v1c_jpeg_image* images, uint64_t workspace_budget, uint32_t* chunks_out);
+
 /* ---- JPEG decoding into a device image (INTEGRATION.md section 8 states the contract; tests/jpgdec_ref.py restates it) ------------
  * Sequential DCT with Huffman coding and 8-bit samples (SOF0, SOF1) in one interleaved scan: one component, or three as JFIF YCbCr
  * in 4:4:4, 4:2:2 or 4:2:0; any DQT, DHT and DRI.  Everything else a JPEG file may be -- progressive, lossless, arithmetic, 12-bit,

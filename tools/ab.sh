@@ -7,6 +7,9 @@
 # calls per file, default 15; each arm's run under LIMIT seconds, default 300 -- a run took well under a minute on an MI355X), one
 # line per file with the median of the device events:
 #   bash tools/ab.sh decode default path/to/parent/libvr180remap.so
+# the workload "encode" likewise: the single-call device JPEG encoder (tools/jpeg_device_bench.py --device-only, RUNS calls per
+# subsampling of the 8192 x 4096 frame), one line per subsampling with the median of the device events:
+#   bash tools/ab.sh encode default path/to/parent/libvr180remap.so
 WLS=$1; shift
 REPS=${REPS:-3}
 TMP=$(mktemp)
@@ -24,6 +27,15 @@ for l in sys.stdin:
     if l.startswith('{'):
         d=json.loads(l); print('$ARM', 'decode:'+d['file'], d['events_ms_min_median_max'][1])
 " >> $TMP ) || { echo "decode run of $ARM failed"; rm -f $TMP; exit 1; }
+        continue
+      fi
+      if [ "$WL" = encode ]; then
+        ( set -o pipefail; env $LIBENV $E timeout -k 10 ${LIMIT:-300} python3 tools/jpeg_device_bench.py --device-only --runs ${RUNS:-15} 2>/dev/null | python3 -c "
+import json,sys
+for l in sys.stdin:
+    if l.startswith('{'):
+        d=json.loads(l); print('$ARM', 'encode:'+d['subsampling'], d['events_ms_min_median_max'][1])
+" >> $TMP ) || { echo "encode run of $ARM failed"; rm -f $TMP; exit 1; }
         continue
       fi
       env $LIBENV $E python3 bench.py --no-cpu-baseline --traffic none --no-cold-extra --workload $WL ${ARGS:-} 2>/dev/null | python3 -c "

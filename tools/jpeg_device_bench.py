@@ -6,7 +6,14 @@ Pillow at the same quality and subsampling).
 and inside a host clock; the call ends in a device synchronisation, so the two agree but for the copy of the scan.  One JSON line per
 subsampling; ``--out`` appends them to a file.
 
+``--batch N [N ...]``: after those lines, one ``encode_jpeg_tensors`` call over N single-eye results of ``--batch-size`` squared
+(default 2048) against N ``encode_jpeg_tensor`` calls in the same process; ``--batch-frames N [N ...]``: the same over N copies of the
+side-by-side frame.  Both ways are warmed up, then alternate run by run (``--batch-runs``, at least 7); each run lies between two
+device events and inside a host clock, and every line carries min / median / max of both, the chunks the batch took and
+``equal_to_single``.  ``--no-single`` leaves the single-frame lines out.
+
     python tools/jpeg_device_bench.py --out profiles/jpeg_device/bench.jsonl
+    python tools/jpeg_device_bench.py --runs 10 --device-only --batch 2 16 64 --batch-frames 2 4 --out profiles/jpeg_encode_batch/bench.jsonl
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/jpeg_device_bench.py --runs 2 --device-only     (per-kernel times)
 """
 from __future__ import annotations
@@ -38,6 +45,50 @@ def result(size: int, dev: torch.device) -> torch.Tensor:
     return sbs
 
 
+def _mmm(v: list[float]) -> list[float]:
+    v = sorted(v)
+    return [round(v[0], 3), round(v[len(v) // 2], 3), round(v[-1], 3)]
+
+
+def batch_lines(images: list[torch.Tensor], what: str, a) -> dict:
+    """one encode_jpeg_tensors call against len(images) encode_jpeg_tensor calls, alternating"""
+    import vr180_convert_amd as V
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        return out, e0.elapsed_time(e1), 1e3 * (time.perf_counter() - t0)
+
+    def loop():
+        return [V.encode_jpeg_tensor(t, quality=a.quality, subsampling=a.batch_subsampling) for t in images]
+
+    def batch():
+        return V.encode_jpeg_tensors(images, quality=a.quality, subsampling=a.batch_subsampling)
+
+    single, _, _ = timed(loop)   # warm-up of both: code objects, the page-locked buffer, the memory pool
+    together, _, _ = timed(batch)
+    chunks = V.last_encode_batch_report()["chunks"]
+    equal = single == together
+    del single, together
+    torch.cuda.synchronize()
+    ev = {"loop": [], "batch": []}
+    host = {"loop": [], "batch": []}
+    for k in range(max(7, a.batch_runs)):
+        for name, fn in (("loop", loop), ("batch", batch)) if k % 2 == 0 else (("batch", batch), ("loop", loop)):
+            _, e, h = timed(fn)
+            ev[name].append(e), host[name].append(h)
+    h, w, cn = (int(v) for v in images[0].shape)
+    return {"batch_of": what, "n": len(images), "shape": [h, w, cn], "quality": a.quality, "subsampling": a.batch_subsampling,
+            "runs": len(ev["loop"]), "chunks": chunks, "equal_to_single": equal,
+            "loop_events_ms_min_median_max": _mmm(ev["loop"]), "batch_events_ms_min_median_max": _mmm(ev["batch"]),
+            "loop_host_ms_min_median_max": _mmm(host["loop"]), "batch_host_ms_min_median_max": _mmm(host["batch"]),
+            "loop_over_batch_median": round(_mmm(ev["loop"])[1] / _mmm(ev["batch"])[1], 3)}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--size", type=int, default=4096, help="output size per eye")
@@ -45,6 +96,12 @@ def main() -> None:
     ap.add_argument("--quality", type=int, default=95)
     ap.add_argument("--device-only", action="store_true", help="skip the host path (profiler runs)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--batch", type=int, nargs="+", default=[], help="list lengths of single-eye results for the batch comparison")
+    ap.add_argument("--batch-frames", type=int, nargs="+", default=[], help="list lengths of side-by-side frames for the batch comparison")
+    ap.add_argument("--batch-size", type=int, default=2048, help="size of a single-eye result of --batch")
+    ap.add_argument("--batch-runs", type=int, default=7)
+    ap.add_argument("--batch-subsampling", default="420")
+    ap.add_argument("--no-single", action="store_true", help="skip the single-frame lines")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("jpeg_device_bench needs the MI355X")
@@ -56,7 +113,15 @@ def main() -> None:
     sbs = result(a.size, dev)
     copies = [sbs.clone() for _ in range(3)]
     h, w, cn = (int(v) for v in sbs.shape)
-    for sub in ("420", "444"):
+    def emit(line: dict) -> None:
+        text = json.dumps(line)
+        print(text, flush=True)
+        if a.out:
+            Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write(text + "\n")
+
+    for sub in () if a.no_single else ("420", "444"):
         def device_path(t):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0 = time.perf_counter()
@@ -91,12 +156,14 @@ def main() -> None:
                 "psnr_db": round(10 * np.log10(255.0 ** 2 / max(mse, 1e-12)), 2),
                 "events_ms_min_median_max": [round(ev[0], 3), round(ev[len(ev) // 2], 3), round(ev[-1], 3)],
                 "mpixel_per_s_median": round(h * w / 1e3 / ev[len(ev) // 2], 1), "device": drun, "host": hrun}
-        text = json.dumps(line)
-        print(text, flush=True)
-        if a.out:
-            Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-            with open(a.out, "a") as f:
-                f.write(text + "\n")
+        emit(line)
+
+    if a.batch:
+        eye = result(a.batch_size, dev)[:, :a.batch_size]
+        for n in a.batch:  # (distinct images: every one the eye shifted by some rows)
+            emit(batch_lines([torch.roll(eye, 8 * k, 0).contiguous() for k in range(n)], "eye", a))
+    for n in a.batch_frames:
+        emit(batch_lines([sbs] + [torch.roll(sbs, 16 * k, 0) for k in range(1, n)], "frame", a))
 
 
 if __name__ == "__main__":

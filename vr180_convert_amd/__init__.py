@@ -19,7 +19,8 @@ from .remapper import (anaglyph_tensors, apply, apply_lr, apply_lr_tensors, auto
                        remap_tensors_auto)
 from .features import detect, match, match_points_device
 from .png_device import encode_png_tensor, imwrite_tensor
-from .jpeg_device import encode_jpeg_tensor, imwrite_jpeg_tensor
+from .jpeg_device import (encode_jpeg_tensor, encode_jpeg_tensors, imwrite_jpeg_tensor, imwrite_jpeg_tensors,
+                          last_encode_batch_report)
 from .jpeg_decode_device import (decode_jpeg_tensor, decode_jpeg_tensors, imread_tensor, imread_tensors, last_batch_report,
                                  last_decode_report)
 from .sharding import remap_sharded
@@ -56,6 +57,10 @@ __all__ = [
     # JPEG files of device-resident results, encoded on the device (device_jpeg=True / --device-jpeg)
     "encode_jpeg_tensor",
     "imwrite_jpeg_tensor",
+    # ... a list of them in shared launches (device_jpeg="batch" / --device-jpeg-batch)
+    "encode_jpeg_tensors",
+    "imwrite_jpeg_tensors",
+    "last_encode_batch_report",
     # JPEG inputs decoded on the device into tensors (device_decode=True / --device-decode)
     "decode_jpeg_tensor",
     "imread_tensor",

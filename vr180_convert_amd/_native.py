@@ -24,7 +24,7 @@ SYMBOLS = [
     "v1c_plan_create_ex", "v1c_remap_lut_ex", "v1c_build_ftab",
     "v1c_feat_detect", "v1c_feat_match", "v1c_feat_pattern",
     "v1c_png_bound", "v1c_png_deflate",
-    "v1c_jpeg_bound", "v1c_jpeg_header", "v1c_jpeg_encode",
+    "v1c_jpeg_bound", "v1c_jpeg_header", "v1c_jpeg_encode", "v1c_jpeg_encode_batch",
     "v1c_jpeg_decode_info", "v1c_jpeg_decode", "v1c_jpeg_decode_batch",
 ]
 
@@ -101,6 +101,10 @@ def lib() -> C.CDLL:
         pass
     try:
         L.v1c_jpeg_decode_batch.argtypes = [i32, vp, i32, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint64, vp, vp, vp]
+    except AttributeError:  # (an older build behind V1C_LIB)
+        pass
+    try:
+        L.v1c_jpeg_encode_batch.argtypes = [i32, vp, i32, vp, C.c_uint64, vp]
     except AttributeError:  # (an older build behind V1C_LIB)
         pass
     L.v1c_plan_run.argtypes = [vp, vp, C.POINTER(_abi.Unit), i32]

@@ -216,6 +216,8 @@ def lr(
                                                                    "time); other formats and --merge are written by the host")] = False,
     device_jpeg: Annotated[bool, typer.Option("--device-jpeg", help="Encode .jpg / .jpeg results on the GPU (baseline JPEG, quality 95, "
                                                                      "4:2:0); other formats and --merge are written by the host")] = False,
+    device_jpeg_batch: Annotated[bool, typer.Option("--device-jpeg-batch", help="As --device-jpeg, with all the results encoded in one "
+                                                                                 "batch that shares its kernel launches")] = False,
     device_decode: Annotated[bool, typer.Option("--device-decode", help="Decode .jpg / .jpeg inputs on the GPU (baseline JPEG; other "
                                                                          "files are read by the host)")] = False,
     device_decode_batch: Annotated[bool, typer.Option("--device-decode-batch", help="As --device-decode, with all the files decoded in one "
@@ -254,7 +256,7 @@ def lr(
         LOG.info(f"Automatched transformer: {chain}")
     apply_lr(chain, left_path=left_in, right_path=right_in, out_path=out, radius=radius_, size_output=parse_size(size),
              interpolation=interp, boarder_mode=border, boarder_value=border_value, merge=merge,
-             **({"device_png": True} if device_png else {}), **({"device_jpeg": True} if device_jpeg else {}),
+             **({"device_png": True} if device_png else {}), **({"device_jpeg": "batch"} if device_jpeg_batch else {"device_jpeg": True} if device_jpeg else {}),
              **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}))
 
 
@@ -272,6 +274,8 @@ def s(
                                                                    "time); other formats and --merge are written by the host")] = False,
     device_jpeg: Annotated[bool, typer.Option("--device-jpeg", help="Encode .jpg / .jpeg results on the GPU (baseline JPEG, quality 95, "
                                                                      "4:2:0); other formats are written by the host")] = False,
+    device_jpeg_batch: Annotated[bool, typer.Option("--device-jpeg-batch", help="As --device-jpeg, with all the results encoded in one "
+                                                                                 "batch that shares its kernel launches")] = False,
     device_decode: Annotated[bool, typer.Option("--device-decode", help="Decode .jpg / .jpeg inputs on the GPU (baseline JPEG; other "
                                                                          "files are read by the host)")] = False,
     device_decode_batch: Annotated[bool, typer.Option("--device-decode-batch", help="As --device-decode, with all the files decoded in one "
@@ -291,7 +295,7 @@ def s(
     apply(parse_transformer(transformer), in_paths=list(in_paths), out_paths=out_paths, radius=parse_radius(radius),
           size_output=parse_size(size), interpolation=_flag(interpolation, _INTERPOLATIONS, "inter_", "interpolation"),
           boarder_mode=_flag(boarder_mode, _BORDERS, "border_", "border mode"), boarder_value=boarder_value,
-          **({"device_png": True} if device_png else {}), **({"device_jpeg": True} if device_jpeg else {}),
+          **({"device_png": True} if device_png else {}), **({"device_jpeg": "batch"} if device_jpeg_batch else {"device_jpeg": True} if device_jpeg else {}),
           **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}))
 
 

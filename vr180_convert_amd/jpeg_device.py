@@ -1,4 +1,5 @@
-"""JPEG files of device-resident results, encoded on the MI355X (``v1c_jpeg_encode``, csrc/kernels_jpeg.hip): colour conversion,
+"""JPEG files of device-resident results, encoded on the MI355X (``v1c_jpeg_encode``, csrc/kernels_jpeg.hip; a list of them in shared
+launches: ``v1c_jpeg_encode_batch``, csrc/kernels_jpeg_batch.hip): colour conversion,
 chroma downsampling, the forward DCT, quantisation, Huffman coding, byte stuffing and the restart markers are HIP kernels, only the
 finished scan comes to the host, and the header segments (``v1c_jpeg_header``) and EOI are put around it here.
 
@@ -10,7 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 from pathlib import Path
-from typing import Any
+from typing import Any, Sequence
 
 import torch
 
@@ -19,6 +20,15 @@ from .remapper import _stream_ptr
 
 SUBSAMPLINGS = {"444": 0, "420": 2}  # V1C_JPEG_444 / V1C_JPEG_420
 HEADER_MAX = 1024                    # V1C_JPEG_HEADER_MAX
+# Bytes of page-locked memory a batch may land in at once (the sum of its images' v1c_jpeg_bound: 3.25 bytes per sample byte of a BGR
+# image in 4:2:0, so 64 results of 2048 x 2048 would pin 1.3 GB); a longer list goes to the engine in several sub-lists.
+PINNED_BUDGET = 1 << 30
+
+
+class JpegImage(C.Structure):
+    """``v1c_jpeg_image`` (include/vr180_remap.h)"""
+    _fields_ = [("img", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("pitch", C.c_int64), ("cn", C.c_int), ("quality", C.c_int),
+                ("subsampling", C.c_int), ("restart_mcus", C.c_int), ("out_host", C.c_void_p), ("capacity", C.c_uint64), ("size", C.c_uint64)]
 
 
 def default_restart_mcus(height: int, width: int, channels: int, subsampling: str = "420") -> int:
@@ -55,7 +65,8 @@ def _image(t: torch.Tensor) -> torch.Tensor:
     return t
 
 
-def _parts(t: torch.Tensor, quality: int, subsampling: str, restart_mcus: int | None) -> list:
+def _params(t: torch.Tensor, quality: int, subsampling: str, restart_mcus: int | None) -> tuple:
+    """the checked arguments of one image: (tensor as the engine takes it, h, w, cn, quality, subsampling code, restart interval)"""
     if subsampling not in SUBSAMPLINGS:
         raise ValueError(f"subsampling must be one of {sorted(SUBSAMPLINGS)}, not {subsampling!r}")
     quality = int(quality)
@@ -68,12 +79,21 @@ def _parts(t: torch.Tensor, quality: int, subsampling: str, restart_mcus: int | 
     restart = default_restart_mcus(h, w, cn, subsampling) if restart_mcus is None else int(restart_mcus)
     if not 1 <= restart <= 65535:
         raise ValueError("restart_mcus must be 1 ... 65535")
-    lib = _native.lib()
-    sub = SUBSAMPLINGS[subsampling]
+    return t, h, w, cn, quality, SUBSAMPLINGS[subsampling], restart
+
+
+def _header(h: int, w: int, cn: int, quality: int, sub: int, restart: int) -> bytes:
     head = (C.c_uint8 * HEADER_MAX)()
-    n = lib.v1c_jpeg_header(h, w, cn, quality, sub, restart, head, HEADER_MAX)
+    n = _native.lib().v1c_jpeg_header(h, w, cn, quality, sub, restart, head, HEADER_MAX)
     if n < 0:
         _native.check(int(n), "v1c_jpeg_header")
+    return bytes(head[:n])
+
+
+def _parts(t: torch.Tensor, quality: int, subsampling: str, restart_mcus: int | None) -> list:
+    t, h, w, cn, quality, sub, restart = _params(t, quality, subsampling, restart_mcus)
+    lib = _native.lib()
+    head = _header(h, w, cn, quality, sub, restart)
     cap = int(lib.v1c_jpeg_bound(h, w, cn, sub, restart))
     dev = t.device
     buf = _host_buffer(dev, cap)
@@ -82,7 +102,7 @@ def _parts(t: torch.Tensor, quality: int, subsampling: str, restart_mcus: int | 
     rc = lib.v1c_jpeg_encode(dev.index, _stream_ptr(dev), t.data_ptr(), h, w, pitch, cn, quality, sub, restart, buf.data_ptr(), buf.numel(),
                              C.byref(size))
     _native.check(rc, "v1c_jpeg_encode")
-    return [bytes(head[:n]), buf.numpy()[:size.value], b"\xff\xd9"]
+    return [head, buf.numpy()[:size.value], b"\xff\xd9"]
 
 
 def encode_jpeg_tensor(t: torch.Tensor, *, quality: int = 95, subsampling: str = "420", restart_mcus: int | None = None) -> bytes:
@@ -100,10 +120,108 @@ def imwrite_jpeg_tensor(path: Any, t: torch.Tensor, *, quality: int = 95, subsam
             f.write(part)
 
 
+_last_encode_batch: dict = {"chunks": 0, "sizes": []}
+
+
+def last_encode_batch_report() -> dict:
+    """``{"chunks": ..., "sizes": [...]}`` of the last ``encode_jpeg_tensors`` / ``imwrite_jpeg_tensors`` call: the chunks the engine ran
+    (two synchronisations each) over all sub-lists, and every image's scan size"""
+    return {"chunks": _last_encode_batch["chunks"], "sizes": list(_last_encode_batch["sizes"])}
+
+
+def _per_image(value: Any, n: int, name: str) -> list:
+    if isinstance(value, (str, bytes)) or not isinstance(value, Sequence):
+        return [value] * n
+    if len(value) != n:
+        raise ValueError(f"{name} has {len(value)} entries for {n} images")
+    return list(value)
+
+
+def sub_lists(bounds: Sequence[int], budget: int | None = None) -> list[tuple[int, int]]:
+    """the ``[lo, hi)`` sub-lists a batch goes to the engine in: images in order while the sum of their bounds stays within the budget
+    of page-locked bytes (``PINNED_BUDGET``, or the largest single bound where that is larger); each holds at least one image"""
+    budget = max(PINNED_BUDGET if budget is None else int(budget), max(bounds, default=0))
+    out, lo, total = [], 0, 0
+    for i, b in enumerate(bounds):
+        if i > lo and total + b > budget:
+            out.append((lo, i))
+            lo, total = i, 0
+        total += b
+    if len(bounds) > lo:
+        out.append((lo, len(bounds)))
+    return out
+
+
+def _batch_parts(tensors: Sequence[torch.Tensor], quality: Any, subsampling: Any, restart_mcus: Any, workspace_budget: int | None):
+    """yields (index, [header, scan, EOI]) of every image, sub-list by sub-list; a scan is a view of the page-locked buffer that holds
+    until the next sub-list is encoded"""
+    n = len(tensors)
+    qs, ss, rs = _per_image(quality, n, "quality"), _per_image(subsampling, n, "subsampling"), _per_image(restart_mcus, n, "restart_mcus")
+    _last_encode_batch["chunks"], _last_encode_batch["sizes"] = 0, []
+    if n == 0:
+        return
+    params = [_params(t, q, s, r) for t, q, s, r in zip(tensors, qs, ss, rs)]
+    devs = {p[0].device for p in params}
+    if len(devs) != 1:
+        raise ValueError(f"the images of a batch must be on one device, not on {sorted(str(d) for d in devs)}")
+    dev = devs.pop()
+    if workspace_budget is not None and int(workspace_budget) < 0:
+        raise ValueError("workspace_budget must not be negative")
+    lib = _native.lib()
+    bounds = [int(lib.v1c_jpeg_bound(h, w, cn, sub, restart)) for _, h, w, cn, _, sub, restart in params]
+    sizes = []
+    for lo, hi in sub_lists(bounds):
+        buf = _host_buffer(dev, sum(bounds[lo:hi]))
+        images = (JpegImage * (hi - lo))()
+        at = 0
+        for k in range(lo, hi):
+            t, h, w, cn, q, sub, restart = params[k]
+            images[k - lo] = JpegImage(t.data_ptr(), h, w, t.stride(0) if h > 1 else w * cn, cn, q, sub, restart, buf.data_ptr() + at, bounds[k], 0)
+            at += bounds[k]
+        chunks = C.c_uint32(0)
+        rc = lib.v1c_jpeg_encode_batch(dev.index, _stream_ptr(dev), hi - lo, images, int(workspace_budget or 0), C.byref(chunks))
+        _native.check(rc, "v1c_jpeg_encode_batch")
+        _last_encode_batch["chunks"] += chunks.value
+        host, at = buf.numpy(), 0
+        for k in range(lo, hi):
+            _, h, w, cn, q, sub, restart = params[k]
+            size = int(images[k - lo].size)
+            sizes.append(size)
+            yield k, [_header(h, w, cn, q, sub, restart), host[at:at + size], b"\xff\xd9"]
+            at += bounds[k]
+    _last_encode_batch["sizes"] = sizes
+
+
+def encode_jpeg_tensors(tensors: Sequence[torch.Tensor], *, quality: Any = 95, subsampling: Any = "420", restart_mcus: Any = None,
+                        workspace_budget: int | None = None) -> list[bytes]:
+    """``encode_jpeg_tensor`` of every tensor of a list in shared launches (``v1c_jpeg_encode_batch``, csrc/kernels_jpeg_batch.hip): every
+    file is byte for byte the single call's.  ``quality``, ``subsampling`` and ``restart_mcus`` are each one value for all images or a
+    sequence of the list's length; the images may differ in size and channels but lie on one device; runs on the current stream.  The
+    engine cuts the list into chunks of at most ``workspace_budget`` bytes of device workspace (``None``: 1 GiB), each of which
+    synchronises twice; a list whose summed ``v1c_jpeg_bound`` passes ``PINNED_BUDGET`` goes to the engine in several sub-lists
+    (``sub_lists``), which multiplies that count a second time.  ``last_encode_batch_report()`` tells what ran."""
+    out: list[bytes] = [b""] * len(tensors)
+    for k, parts in _batch_parts(tensors, quality, subsampling, restart_mcus, workspace_budget):
+        out[k] = b"".join(bytes(p) for p in parts)
+    return out
+
+
+def imwrite_jpeg_tensors(paths: Sequence[Any], tensors: Sequence[torch.Tensor], *, quality: Any = 95, subsampling: Any = "420",
+                         restart_mcus: Any = None, workspace_budget: int | None = None) -> None:
+    """``encode_jpeg_tensors`` into files (every scan goes from the page-locked buffer to its file without a copy in between)"""
+    if len(paths) != len(tensors):
+        raise ValueError(f"{len(paths)} paths for {len(tensors)} images")
+    for k, parts in _batch_parts(tensors, quality, subsampling, restart_mcus, workspace_budget):
+        with open(paths[k], "wb") as f:
+            for part in parts:
+                f.write(part)
+
+
 def eligible(path: Any, result: Any) -> bool:
     """whether ``device_jpeg=True`` writes this result through the device encoder: a ``.jpg`` / ``.jpeg`` path and a uint8 device tensor"""
     return (isinstance(path, (str, Path)) and Path(path).suffix.lower() in (".jpg", ".jpeg") and isinstance(result, torch.Tensor)
             and result.is_cuda and result.dtype == torch.uint8)
 
 
-__all__ = ["encode_jpeg_tensor", "imwrite_jpeg_tensor", "default_restart_mcus", "eligible"]
+__all__ = ["encode_jpeg_tensor", "imwrite_jpeg_tensor", "encode_jpeg_tensors", "imwrite_jpeg_tensors", "last_encode_batch_report",
+           "default_restart_mcus", "eligible"]

@@ -687,6 +687,13 @@ def _decode_on_device(items: Sequence[Any], device: Any, mode: Any = True) -> li
     return jpeg_decode_device.read_inputs(items, device=device)
 
 
+def _device_jpeg_mode(mode: Any) -> Any:
+    """``device_jpeg``: False, True (a call of the device encoder per result) or ``"batch"`` (one call for all of them)"""
+    if isinstance(mode, str) and mode != "batch":
+        raise ValueError('device_jpeg must be True, False or "batch"')
+    return mode
+
+
 def apply(
     transformer: TransformerBase,
     *,
@@ -699,7 +706,7 @@ def apply(
     radius: float | Literal["auto", "max"] = "auto",
     device: Any = None,
     device_png: bool = False,
-    device_jpeg: bool = False,
+    device_jpeg: bool | Literal["batch"] = False,
     device_decode: bool | Literal["batch"] = False,
 ) -> Sequence[NDArray[np.uint8]]:
     """Apply transformer to images (reference remapper.py:324-403).
@@ -712,7 +719,13 @@ def apply(
     ``device_decode=True``: ``.jpg`` / ``.jpeg`` inputs are decoded on the device (jpeg_decode_device.py) and take the device-resident
     route -- with anything that came from the host reader uploaded to join them --, so the results are CUDA tensors; files outside the
     device decoder's scope are read by the host as before.  ``device_decode="batch"``: the same, with all the files decoded in one
-    batch that shares its launches and synchronisation rounds (jpeg_decode_device.decode_jpeg_tensors)."""
+    batch that shares its launches and synchronisation rounds (jpeg_decode_device.decode_jpeg_tensors).
+
+    ``device_jpeg=True``: every ``.jpg`` / ``.jpeg`` result that is a uint8 tensor on the device is encoded there, one call of the
+    encoder per result (jpeg_device.imwrite_jpeg_tensor).  ``device_jpeg="batch"``: all of them in ONE call that shares its launches
+    and its two synchronisations (jpeg_device.imwrite_jpeg_tensors); the files are the same bytes.  The other results take the paths
+    they take without it (``device_png``, the host writer)."""
+    device_jpeg = _device_jpeg_mode(device_jpeg)
     in_paths_ = [in_paths] if isinstance(in_paths, (str, Path, np.ndarray, torch.Tensor)) else in_paths
     out_paths_ = [out_paths] if isinstance(out_paths, (str, Path)) else out_paths
     del in_paths, out_paths
@@ -772,8 +785,12 @@ def apply(
 
                 writers.append((jpeg_device.eligible, jpeg_device.imwrite_jpeg_tensor))
             on_dev = [next((write for ok, write in writers if ok(q, d)), None) for q, d in zip(paths, dsts)]
+            if device_jpeg == "batch":  # the eligible results in one call, in order; the writer above only marks them
+                together = [i for i, write in enumerate(on_dev) if write is jpeg_device.imwrite_jpeg_tensor]
+                if together:
+                    jpeg_device.imwrite_jpeg_tensors([paths[i] for i in together], [dsts[i] for i in together])
             for q, d, write in zip(paths, dsts, on_dev):
-                if write:
+                if write and not (device_jpeg == "batch" and write is jpeg_device.imwrite_jpeg_tensor):
                     write(q, d)
             keep = [i for i, ok in enumerate(on_dev) if not ok]
             paths, results_ = [paths[i] for i in keep], [results[i] for i in keep]
@@ -983,7 +1000,7 @@ def apply_lr(
     merge: bool = False,
     device: Any = None,
     device_png: bool = False,
-    device_jpeg: bool = False,
+    device_jpeg: bool | Literal["batch"] = False,
     device_decode: bool | Literal["batch"] = False,
 ) -> None:
     """Apply transformer to a pair of images and save them side by side (reference
@@ -992,10 +1009,12 @@ def apply_lr(
     ``device_png=True``: a ``.png`` ``out_path`` of a uint8 / uint16 side-by-side result is deflated on the device
     (png_device.imwrite_tensor) and the raw result is not copied to the host; ``merge=True`` and other formats take the host route.
     ``device_jpeg=True``: the same for a ``.jpg`` / ``.jpeg`` ``out_path`` of a uint8 result (jpeg_device.imwrite_jpeg_tensor:
-    quality 95, 4:2:0, as the host writer).
+    quality 95, 4:2:0, as the host writer).  ``device_jpeg="batch"``: accepted as in ``apply``; the side-by-side frame is a batch of
+    one (jpeg_device.imwrite_jpeg_tensors), the same bytes.
     ``device_decode=True``: ``.jpg`` / ``.jpeg`` inputs are decoded on the device (jpeg_decode_device.py) and only their bytes are
     uploaded; one file holding both eyes is decoded once and the halves are views of it.  Files outside the device decoder's scope
     are read by the host as before.  ``device_decode="batch"``: the same, with the two files decoded as one batch of two."""
+    device_jpeg = _device_jpeg_mode(device_jpeg)
     if device_decode:
         if isinstance(left_path, (str, Path)) and isinstance(right_path, (str, Path)) and left_path == right_path:
             both = _decode_on_device([left_path], device, device_decode)[0]
@@ -1042,7 +1061,10 @@ def apply_lr(
             from . import jpeg_device
 
             if jpeg_device.eligible(out_path, sbs):
-                jpeg_device.imwrite_jpeg_tensor(out_path, sbs)
+                if device_jpeg == "batch":
+                    jpeg_device.imwrite_jpeg_tensors([out_path], [sbs])
+                else:
+                    jpeg_device.imwrite_jpeg_tensor(out_path, sbs)
                 LOG.info(f"Saved to {Path(out_path).absolute()}")
                 return
         combine = sbs.cpu().numpy()
