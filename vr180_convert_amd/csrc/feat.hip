@@ -12,10 +12,7 @@
 
 #include "../../include/vr180_remap.h"
 #include "feat_launch.hpp"
-
-namespace v1c {
-int set_error(int code, const std::string& msg);  // plan.hip: the message v1c_last_error returns
-}
+#include "host_util.hpp"
 
 using namespace v1c;
 using namespace v1c::feat;
@@ -28,22 +25,6 @@ using namespace v1c::feat;
     } while (0)
 
 namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess)
-            prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
 
 #pragma clang fp contract(off)
 
@@ -138,11 +119,6 @@ int device_tables(int device, const int8_t** pattern, const int32_t** bv)
     *pattern = (const int8_t*)d;
     *bv = (const int32_t*)((const uint8_t*)d + kPatternBytes);
     return V1C_OK;
-}
-
-size_t align256(size_t n)
-{
-    return (n + 255) & ~(size_t)255;
 }
 
 }  // namespace

@@ -8,51 +8,15 @@
 #include <vector>
 
 #include "../../include/vr180_remap.h"
+#include "host_util.hpp"
 #include "jpeg_batch.hpp"
 #include "jpeg_host.hpp"
 #include "jpeg_launch.hpp"
-
-namespace v1c {
-int set_error(int code, const std::string& msg);  // plan.hip: the message v1c_last_error returns
-}
 
 using namespace v1c;
 using namespace v1c::jpeg;
 
 namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess)
-            prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
-
-size_t align256(size_t n)
-{
-    return (n + 255) & ~(size_t)255;
-}
-
-// the stream-ordered workspace of one call, released on every way out
-struct Workspace {
-    uint8_t* p = nullptr;
-    hipStream_t st;
-    explicit Workspace(hipStream_t s) : st(s) {}
-    ~Workspace()
-    {
-        if (p)
-            (void)hipFreeAsync(p, st);
-    }
-};
 
 // the argument rules of one image, for the single call and for every image of a batch: what is wrong, or nothing; g: its geometry
 std::string image_error(const void* img, int h, int w, int64_t pitch, int cn, int quality, int subsampling, int restart_mcus,
@@ -77,6 +41,39 @@ std::string image_error(const void* img, int h, int w, int64_t pitch, int cn, in
     return std::string();
 }
 
+// The workspace of a call on ws: the `head` bytes the call lays out itself, and behind them the encoder's buffers for `t` entries back to
+// back, each aligned to 256 bytes.
+struct BufferSet {
+    Buffers buf;
+    size_t raw_bytes;  // of buf.raw, to be zeroed
+    size_t bytes;      // of the workspace, head included
+};
+
+hipError_t allocate_buffers(Workspace& ws, size_t head, const Totals& t, BufferSet& s)
+{
+    s.raw_bytes = align256(t.pieces * kPiece + 16);
+    const size_t o_coef = head, o_bits = o_coef + align256(t.nblocks * 128), o_bitoff = o_bits + align256(t.nblocks * 4);
+    const size_t o_ibytes = o_bitoff + align256((t.nblocks + 1) * 8), o_ioff = o_ibytes + align256(t.nint * 4);
+    const size_t o_raw = o_ioff + align256((t.nint + 1) * 8), o_ffcnt = o_raw + s.raw_bytes, o_ffoff = o_ffcnt + align256(t.pieces * 4);
+    const size_t o_sums = o_ffoff + align256((t.pieces + 1) * 8), o_out = o_sums + align256(sums_of(t, kScanChunk) * 8);
+    s.bytes = o_out + align256(t.out_bytes + 8);
+    const hipError_t e = hipMallocAsync((void**)&ws.p, s.bytes, ws.st);
+    if (e != hipSuccess)
+        return e;
+    uint8_t* base = ws.p;
+    s.buf.coef = (int16_t*)(base + o_coef);
+    s.buf.bits = (uint32_t*)(base + o_bits);
+    s.buf.bitoff = (uint64_t*)(base + o_bitoff);
+    s.buf.ibytes = (uint32_t*)(base + o_ibytes);
+    s.buf.ioff = (uint64_t*)(base + o_ioff);
+    s.buf.raw = (uint32_t*)(base + o_raw);
+    s.buf.ffcnt = (uint32_t*)(base + o_ffcnt);
+    s.buf.ffoff = (uint64_t*)(base + o_ffoff);
+    s.buf.sums = (uint64_t*)(base + o_sums);
+    s.buf.out = base + o_out;
+    return hipSuccess;
+}
+
 // One chunk of a batch: images [lo, hi) in one allocation, one upload and one chain of kernels; then all sizes and synchronisation 1,
 // every image's scan and synchronisation 2.
 hipError_t encode_chunk(hipStream_t st, v1c_jpeg_image* images, const std::vector<Geom>& geoms, uint32_t lo, uint32_t hi, std::string& what)
@@ -92,8 +89,8 @@ hipError_t encode_chunk(hipStream_t st, v1c_jpeg_image* images, const std::vecto
             quality.push_back(images[lo + f].quality);
     }
     const size_t o_im = 0, o_first = o_im + align256((size_t)n * sizeof(Image)), o_tabs = o_first + align256((size_t)kWorkLists * (n + 1) * 4);
-    const size_t head = o_tabs + align256(quality.size() * sizeof(Tables));
-    std::vector<uint8_t> up(head, 0);  // (pageable: alive until the first synchronisation below, on every way out)
+    const size_t o_sizes = o_tabs + align256(quality.size() * sizeof(Tables)), head = o_sizes + align256((size_t)n * 8);
+    std::vector<uint8_t> up(o_sizes, 0);  // (pageable: alive until the first synchronisation below, on every way out)
     Image* im = (Image*)(up.data() + o_im);
     uint32_t* first = (uint32_t*)(up.data() + o_first);
     for (uint32_t f = 0; f < n; f++) {
@@ -104,37 +101,23 @@ hipError_t encode_chunk(hipStream_t st, v1c_jpeg_image* images, const std::vecto
     for (size_t k = 0; k < quality.size(); k++)
         make_tables(quality[k], ((Tables*)(up.data() + o_tabs))[k]);
 
-    const size_t raw_bytes = align256(t.pieces * kPiece + 16);
-    const size_t o_sizes = head, o_coef = o_sizes + align256((size_t)n * 8), o_bits = o_coef + align256(t.nblocks * 128);
-    const size_t o_bitoff = o_bits + align256(t.nblocks * 4), o_ibytes = o_bitoff + align256((t.nblocks + 1) * 8);
-    const size_t o_ioff = o_ibytes + align256(t.nint * 4), o_raw = o_ioff + align256((t.nint + 1) * 8), o_ffcnt = o_raw + raw_bytes;
-    const size_t o_ffoff = o_ffcnt + align256(t.pieces * 4), o_sums = o_ffoff + align256((t.pieces + 1) * 8);
-    const size_t o_out = o_sums + align256(sums_of(t, kScanChunk) * 8), bytes = o_out + align256(t.out_bytes + 8);
     Workspace ws(st);
     what = "hipMallocAsync";
-    hipError_t e = hipMallocAsync((void**)&ws.p, bytes, st);
+    BufferSet bs;
+    hipError_t e = allocate_buffers(ws, head, t, bs);
     if (e != hipSuccess)
         return e;
     Batch b{};
     b.im = (const Image*)(ws.p + o_im), b.first = (const uint32_t*)(ws.p + o_first), b.tabs = (const Tables*)(ws.p + o_tabs);
     b.n = n, b.t = t;
     b.sizes = (uint64_t*)(ws.p + o_sizes);
-    b.coef = (int16_t*)(ws.p + o_coef);
-    b.bits = (uint32_t*)(ws.p + o_bits);
-    b.bitoff = (uint64_t*)(ws.p + o_bitoff);
-    b.ibytes = (uint32_t*)(ws.p + o_ibytes);
-    b.ioff = (uint64_t*)(ws.p + o_ioff);
-    b.raw = (uint32_t*)(ws.p + o_raw);
-    b.ffcnt = (uint32_t*)(ws.p + o_ffcnt);
-    b.ffoff = (uint64_t*)(ws.p + o_ffoff);
-    b.sums = (uint64_t*)(ws.p + o_sums);
-    b.out = ws.p + o_out;
+    b.buf = bs.buf;
 
     what = "kernels";
     std::vector<uint64_t> sizes(n, 0);
-    e = hipMemcpyAsync(ws.p, up.data(), head, hipMemcpyHostToDevice, st);
+    e = hipMemcpyAsync(ws.p, up.data(), o_sizes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
-        e = hipMemsetAsync(b.raw, 0, raw_bytes, st);
+        e = hipMemsetAsync(b.buf.raw, 0, bs.raw_bytes, st);
     if (e == hipSuccess)
         e = hipMemsetAsync(b.sizes, 0, (size_t)n * 8, st);
     if (e == hipSuccess)
@@ -152,7 +135,7 @@ hipError_t encode_chunk(hipStream_t st, v1c_jpeg_image* images, const std::vecto
             return hipErrorUnknown;
     what = "copy";
     for (uint32_t f = 0; f < n && e == hipSuccess; f++)
-        e = hipMemcpyAsync(images[lo + f].out_host, b.out + im[f].out0, sizes[f], hipMemcpyDeviceToHost, st);
+        e = hipMemcpyAsync(images[lo + f].out_host, b.buf.out + im[f].out0, sizes[f], hipMemcpyDeviceToHost, st);
     const hipError_t ec = hipStreamSynchronize(st);  // 2: the scans
     if (e == hipSuccess)
         e = ec;
@@ -198,16 +181,11 @@ extern "C" int v1c_jpeg_encode(int device, void* stream, const void* img, int h,
     if (!dg.ok)
         return set_error(V1C_E_NODEVICE, "hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
-    const uint64_t nraw = raw_bound(g), pieces = nraw / kPiece;
-    const uint64_t nsums = std::max<uint64_t>((pieces + kScanChunk - 1) / kScanChunk, ((uint64_t)g.nblocks + kScanChunk - 1) / kScanChunk) + 1;
-    const size_t o_tab = 0, o_total = o_tab + align256(sizeof(Tables)), o_coef = o_total + 256;
-    const size_t o_bits = o_coef + align256((size_t)g.nblocks * 128), o_bitoff = o_bits + align256((size_t)g.nblocks * 4);
-    const size_t o_ibytes = o_bitoff + align256(((size_t)g.nblocks + 1) * 8), o_ioff = o_ibytes + align256((size_t)g.nint * 4);
-    const size_t o_raw = o_ioff + align256(((size_t)g.nint + 1) * 8), o_ffcnt = o_raw + align256(nraw + 16);
-    const size_t o_ffoff = o_ffcnt + align256(pieces * 4), o_sums = o_ffoff + align256((pieces + 1) * 8);
-    const size_t o_out = o_sums + align256(nsums * 8), bytes = o_out + align256(cap + 8);
+    const Totals t{g.nblocks, g.nint, pieces_of(g), cap};
+    const size_t o_tab = 0, o_total = o_tab + align256(sizeof(Tables)), head = o_total + 256;
     Workspace ws(st);
-    hipError_t e = hipMallocAsync((void**)&ws.p, bytes, st);
+    BufferSet bs;
+    hipError_t e = allocate_buffers(ws, head, t, bs);
     if (e != hipSuccess)
         return set_error(V1C_E_HIP, std::string("v1c_jpeg_encode: hipMallocAsync: ") + hipGetErrorString(e));
     Args a{};
@@ -216,23 +194,14 @@ extern "C" int v1c_jpeg_encode(int device, void* stream, const void* img, int h,
     a.g = g;
     a.tab = (const Tables*)(ws.p + o_tab);
     a.total = (uint64_t*)(ws.p + o_total);
-    a.coef = (int16_t*)(ws.p + o_coef);
-    a.bits = (uint32_t*)(ws.p + o_bits);
-    a.bitoff = (uint64_t*)(ws.p + o_bitoff);
-    a.ibytes = (uint32_t*)(ws.p + o_ibytes);
-    a.ioff = (uint64_t*)(ws.p + o_ioff);
-    a.raw = (uint32_t*)(ws.p + o_raw);
-    a.ffcnt = (uint32_t*)(ws.p + o_ffcnt);
-    a.ffoff = (uint64_t*)(ws.p + o_ffoff);
-    a.sums = (uint64_t*)(ws.p + o_sums);
-    a.out = ws.p + o_out;
+    a.buf = bs.buf;
 
     Tables tab;  // (pageable: alive until the first synchronisation below, on every way out)
     make_tables(quality, tab);
     uint64_t total = 0;
     e = hipMemcpyAsync(ws.p + o_tab, &tab, sizeof(tab), hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
-        e = hipMemsetAsync(a.raw, 0, align256(nraw + 16), st);
+        e = hipMemsetAsync(a.buf.raw, 0, bs.raw_bytes, st);
     if (e == hipSuccess)
         e = hipMemsetAsync(a.total, 0, 8, st);
     if (e == hipSuccess)
@@ -246,7 +215,7 @@ extern "C" int v1c_jpeg_encode(int device, void* stream, const void* img, int h,
         return set_error(V1C_E_HIP, std::string("v1c_jpeg_encode (kernels): ") + hipGetErrorString(e));
     if (total == 0 || total > cap)
         return set_error(V1C_E_HIP, "v1c_jpeg_encode: internal size estimate exceeded");
-    e = hipMemcpyAsync(out_host, a.out, total, hipMemcpyDeviceToHost, st);
+    e = hipMemcpyAsync(out_host, a.buf.out, total, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess)
         e = hipStreamSynchronize(st);  // 2: the scan
     if (e != hipSuccess)
@@ -277,8 +246,7 @@ extern "C" int v1c_jpeg_encode_batch(int device, void* stream, int n, v1c_jpeg_i
     if (!dg.ok)
         return set_error(V1C_E_NODEVICE, "hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    if (stream_is_capturing(st))
         return set_error(V1C_E_UNSUPPORTED, "v1c_jpeg_encode_batch: the host reads the sizes between the kernels and the copies, so the call cannot be captured into a graph");
     std::vector<uint64_t> bytes, groups;
     for (int i = 0; i < n; i++) {

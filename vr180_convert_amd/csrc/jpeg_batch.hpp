@@ -3,7 +3,9 @@
 // image, the values that turn a scan over the concatenation into the single call's, and the cut of a list into chunks under a
 // workspace budget.  DESIGN.md section 16.
 //
-// __host__ __device__ / plain C++ so that tests/host_jpeg_batch/ runs exactly this code in its sequential copy of the kernels.
+// The values relative to an image are what the stages' bodies (jpeg_kernels.hpp) compute with for the single call too, whose image has
+// its regions at zero.  __host__ __device__ / plain C++ so that tests/host_jpeg_batch/ runs exactly this code in its sequential copy of
+// the kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,6 +14,7 @@
 #include <vector>
 
 #include "jpeg_core.hpp"
+#include "jpeg_launch.hpp"
 #include "jpegdec_batch.hpp"
 
 namespace v1c {
@@ -145,16 +148,7 @@ struct Batch {
     const Tables* tabs;     // one per distinct quality of the chunk
     uint32_t n;
     Totals t;
-    int16_t* coef;          // the buffers of jpeg_launch.hpp's Args, every image's region back to back
-    uint32_t* bits;
-    uint64_t* bitoff;       // t.nblocks + 1: the scan over all images' blocks
-    uint32_t* ibytes;
-    uint64_t* ioff;         // t.nint + 1
-    uint32_t* raw;          // zeroed; every image's region starts on a piece
-    uint32_t* ffcnt;
-    uint64_t* ffoff;        // t.pieces + 1
-    uint64_t* sums;
-    uint8_t* out;
+    Buffers buf;            // every image's region back to back; bitoff, ioff and ffoff are the scans over all images' entries
     uint64_t* sizes;        // n: every image's scan size, zeroed
 };
 

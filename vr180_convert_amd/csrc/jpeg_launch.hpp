@@ -1,4 +1,5 @@
-// jpeg_launch.hpp -- launcher of the JPEG encoder's kernels (kernels_jpeg.hip), called by the C ABI in jpeg.hip.
+// jpeg_launch.hpp -- the buffer set of the JPEG encoder's kernels and the launcher of the single call's (kernels_jpeg.hip), called by
+// the C ABI in jpeg.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,22 +12,28 @@ namespace jpeg {
 
 constexpr uint32_t kScanChunk = 2048;  // entries one workgroup of the scans takes
 
-struct Args {
-    const uint8_t* img;
-    int64_t pitch;
-    Geom g;
-    const Tables* tab;
+// The buffers the stages hand on to each other, for one image (Args) or for the images of a chunk, every image's region back to back
+// (Batch, jpeg_batch.hpp).  The stages' bodies (jpeg_kernels.hpp) know no more of their caller than this.
+struct Buffers {
     int16_t* coef;       // nblocks x 64 quantised coefficients in zigzag order, MCU-major
     uint32_t* bits;      // coded bits of every block
     uint64_t* bitoff;    // nblocks + 1: their exclusive scan
     uint32_t* ibytes;    // bytes of every interval with its pad, before stuffing
     uint64_t* ioff;      // nint + 1: their exclusive scan
-    uint32_t* raw;       // the intervals back to back before stuffing, zeroed; raw_bound bytes
+    uint32_t* raw;       // the intervals back to back before stuffing, zeroed; whole pieces, an image's region starts on one
     uint32_t* ffcnt;     // 0xFF bytes of every kPiece bytes of raw
     uint64_t* ffoff;     // pieces + 1: their exclusive scan
     uint64_t* sums;      // the scans' per-chunk sums
-    uint8_t* out;        // the scan: stuffed intervals and RSTm markers
-    uint64_t* total;     // its size
+    uint8_t* out;        // the scans: stuffed intervals and RSTm markers
+};
+
+struct Args {
+    const uint8_t* img;
+    int64_t pitch;
+    Geom g;
+    const Tables* tab;
+    Buffers buf;
+    uint64_t* total;     // the scan's size
 };
 
 // every kernel of one image, in order, on `st`; nothing synchronises

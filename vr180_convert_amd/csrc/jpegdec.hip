@@ -10,45 +10,14 @@
 #include <vector>
 
 #include "../../include/vr180_remap.h"
+#include "host_util.hpp"
 #include "jpegdec_host.hpp"
 #include "jpegdec_launch.hpp"
-
-namespace v1c {
-int set_error(int code, const std::string& msg);  // plan.hip: the message v1c_last_error returns
-}
 
 using namespace v1c;
 using namespace v1c::jpegdec;
 
 namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess)
-            prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
-
-// the stream-ordered workspace of one call, released on every way out
-struct Workspace {
-    uint8_t* p = nullptr;
-    hipStream_t st;
-    explicit Workspace(hipStream_t s) : st(s) {}
-    ~Workspace()
-    {
-        if (p)
-            (void)hipFreeAsync(p, st);
-    }
-};
 
 // The page-locked staging buffers, one per device, grown on demand and kept: what is uploaded (tables, segment offsets, the scan) and
 // the word that comes back.  Each has a lock of its own, held by a call from filling the buffer to its last synchronisation, so the
@@ -77,12 +46,37 @@ uint8_t* staging(Staging& s, size_t bytes)
     return s.p;
 }
 
-int parse_error(const char* who, ParseResult r, const Parsed& p, v1c_jpeg_decode_report* report)
+// the code of a parse that failed, and what it found
+int parse_error(ParseResult r, const Parsed& p, std::string& why)
 {
-    if (report)
-        report->error_pos = p.error_pos;
-    return set_error(r == kUnsupported ? V1C_E_UNSUPPORTED : V1C_E_CORRUPT,
-                     std::string(who) + ": " + p.why + " (byte " + std::to_string(p.error_pos) + ")");
+    why = p.why + " (byte " + std::to_string(p.error_pos) + ")";
+    return r == kUnsupported ? V1C_E_UNSUPPORTED : V1C_E_CORRUPT;
+}
+
+// The bits of a subsequence that subseq_bits asks for, or 0 where it breaks the rule.
+uint32_t subseq_of(uint32_t subseq_bits)
+{
+    const uint32_t S = subseq_bits ? subseq_bits : kDefaultSubseqBits;
+    return S % 32 || S < 256 || S > (1u << 24) ? 0 : S;
+}
+const char* const kSubseqRule = "subseq_bits must be a multiple of 32 from 256 to 2^24, or 0";
+
+// Whether a file can be decoded into its destination, for the single call and for every file of a batch: V1C_OK and the parse in ps, or
+// the code and what is wrong.  Where the parse refused the file, ps.error_pos has the byte.
+int file_error(const uint8_t* file, uint64_t size, const void* out, int64_t pitch, int out_cn, Parsed& ps, std::string& why)
+{
+    if (!file || !out)
+        return why = "NULL pointer", V1C_E_INVALID;
+    if (out_cn != 1 && out_cn != 3)
+        return why = "out_cn must be 1 or 3", V1C_E_INVALID;
+    const ParseResult pr = parse(file, size, ps);
+    if (pr != kParsed)
+        return parse_error(pr, ps, why);
+    if (out_cn == 1 && ps.g.nc != 1)
+        return why = "out_cn 1 takes a file of one component", V1C_E_INVALID;
+    if (pitch < (int64_t)ps.g.w * out_cn)
+        return why = "pitch is smaller than a row's bytes", V1C_E_INVALID;
+    return V1C_OK;
 }
 
 }  // namespace
@@ -93,8 +87,11 @@ extern "C" int v1c_jpeg_decode_info(const uint8_t* file, uint64_t size, v1c_jpeg
         return set_error(V1C_E_INVALID, "v1c_jpeg_decode_info: NULL pointer");
     Parsed p;
     const ParseResult r = parse(file, size, p);
-    if (r != kParsed)
-        return parse_error("v1c_jpeg_decode_info", r, p, nullptr);
+    if (r != kParsed) {
+        std::string why;
+        const int code = parse_error(r, p, why);
+        return set_error(code, "v1c_jpeg_decode_info: " + why);
+    }
     info->height = (int32_t)p.g.h, info->width = (int32_t)p.g.w, info->components = (int32_t)p.g.nc;
     info->h_samp = (int32_t)p.g.hs, info->v_samp = (int32_t)p.g.vs, info->restart_interval = (int32_t)p.restart;
     return V1C_OK;
@@ -105,22 +102,18 @@ extern "C" int v1c_jpeg_decode(int device, void* stream, const uint8_t* file, ui
 {
     if (report)
         std::memset(report, 0, sizeof(*report));
-    if (!file || !out)
-        return set_error(V1C_E_INVALID, "v1c_jpeg_decode: NULL pointer");
-    if (out_cn != 1 && out_cn != 3)
-        return set_error(V1C_E_INVALID, "v1c_jpeg_decode: out_cn must be 1 or 3");
-    const uint32_t S = subseq_bits ? subseq_bits : kDefaultSubseqBits;
-    if (S % 32 || S < 256 || S > (1u << 24))
-        return set_error(V1C_E_INVALID, "v1c_jpeg_decode: subseq_bits must be a multiple of 32 from 256 to 2^24, or 0");
+    const uint32_t S = subseq_of(subseq_bits);
+    if (!S)
+        return set_error(V1C_E_INVALID, std::string("v1c_jpeg_decode: ") + kSubseqRule);
     Parsed ps;
-    const ParseResult pr = parse(file, size, ps);
-    if (pr != kParsed)
-        return parse_error("v1c_jpeg_decode", pr, ps, report);
+    std::string why;
+    const int bad = file_error(file, size, out, pitch, out_cn, ps, why);
+    if (bad != V1C_OK) {
+        if (report)
+            report->error_pos = ps.error_pos;
+        return set_error(bad, "v1c_jpeg_decode: " + why);
+    }
     const Geom& g = ps.g;
-    if (out_cn == 1 && g.nc != 1)
-        return set_error(V1C_E_INVALID, "v1c_jpeg_decode: out_cn 1 takes a file of one component");
-    if (pitch < (int64_t)g.w * out_cn)
-        return set_error(V1C_E_INVALID, "v1c_jpeg_decode: pitch is smaller than a row's bytes");
 
     if (device < 0 || device >= kMaxDevices)
         return set_error(V1C_E_NODEVICE, "v1c_jpeg_decode: no such device");
@@ -128,8 +121,7 @@ extern "C" int v1c_jpeg_decode(int device, void* stream, const uint8_t* file, ui
     if (!dg.ok)
         return set_error(V1C_E_NODEVICE, "hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    if (stream_is_capturing(st))
         return set_error(V1C_E_UNSUPPORTED, "v1c_jpeg_decode: the host reads a flag between the rounds, so the call cannot be captured into a graph");
 
     const std::vector<uint32_t> subfirst = sub_first(ps, S);
@@ -334,9 +326,9 @@ extern "C" int v1c_jpeg_decode_batch(int device, void* stream, int n, const uint
         return V1C_OK;
     if (!files || !sizes || !outs || !pitches || !out_cns || !status || !reports)
         return set_error(V1C_E_INVALID, "v1c_jpeg_decode_batch: NULL pointer");
-    const uint32_t S = subseq_bits ? subseq_bits : kDefaultSubseqBits;
-    if (S % 32 || S < 256 || S > (1u << 24))
-        return set_error(V1C_E_INVALID, "v1c_jpeg_decode_batch: subseq_bits must be a multiple of 32 from 256 to 2^24, or 0");
+    const uint32_t S = subseq_of(subseq_bits);
+    if (!S)
+        return set_error(V1C_E_INVALID, std::string("v1c_jpeg_decode_batch: ") + kSubseqRule);
     // (device and capture first: under capture nothing is done, not even a status written)
     if (device < 0 || device >= kMaxDevices)
         return set_error(V1C_E_NODEVICE, "v1c_jpeg_decode_batch: no such device");
@@ -344,8 +336,7 @@ extern "C" int v1c_jpeg_decode_batch(int device, void* stream, int n, const uint
     if (!dg.ok)
         return set_error(V1C_E_NODEVICE, "hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    if (stream_is_capturing(st))
         return set_error(V1C_E_UNSUPPORTED, "v1c_jpeg_decode_batch: the host reads a flag between the rounds, so the call cannot be captured into a graph");
     std::memset(reports, 0, sizeof(*reports) * (size_t)n);
 
@@ -353,25 +344,16 @@ extern "C" int v1c_jpeg_decode_batch(int device, void* stream, int n, const uint
     std::vector<BatchFile> good;
     good.reserve((size_t)n);
     for (int i = 0; i < n; i++) {
-        status[i] = V1C_OK;
-        if (!files[i] || !outs[i] || (out_cns[i] != 1 && out_cns[i] != 3)) {
-            status[i] = V1C_E_INVALID;
-            continue;
-        }
         good.emplace_back();
         BatchFile& bf = good.back();
-        const ParseResult pr = parse(files[i], sizes[i], bf.ps);
-        const Geom& g = bf.ps.g;
-        if (pr != kParsed) {
-            status[i] = pr == kUnsupported ? V1C_E_UNSUPPORTED : V1C_E_CORRUPT;
-            reports[i].error_pos = bf.ps.error_pos;
-        } else if ((out_cns[i] == 1 && g.nc != 1) || pitches[i] < (int64_t)g.w * out_cns[i]) {
-            status[i] = V1C_E_INVALID;
-        }
+        std::string why;  // (a file of a batch has a status, no message)
+        status[i] = file_error(files[i], sizes[i], outs[i], pitches[i], out_cns[i], bf.ps, why);
         if (status[i] != V1C_OK) {
+            reports[i].error_pos = bf.ps.error_pos;
             good.pop_back();
             continue;
         }
+        const Geom& g = bf.ps.g;
         bf.index = i;
         bf.subfirst = sub_first(bf.ps, S);
         bf.nsub = bf.subfirst.back();

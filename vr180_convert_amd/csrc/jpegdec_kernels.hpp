@@ -1,10 +1,11 @@
 // jpegdec_kernels.hpp -- what one workgroup of every kernel of the device JPEG decoder does, given its file's Args BY REFERENCE and its
-// index within the file: the bodies of the kernels of a batch (kernels_jpegdec_batch.hip), where a workgroup first looks up its file
-// (jpegdec_batch.hpp) and the Args lie in device memory.  They are kernels_jpegdec.hip's kernels line for line, with blockIdx.x replaced
-// by the index within the file and the flag words named by the caller.  kernels_jpegdec.hip keeps its own text, so that the single-file
-// call's code object stays the one it was (the same bodies compiled there give other machine code; by value they go to scratch).  The
-// per-lane arithmetic is jpegdec_core.hpp's in both; tests/test_gpu_jpegdec_batch.py holds the two forms to each other sample for
-// sample, report for report.  Device code only.
+// index within the file: the one text of the eight stages.  kernels_jpegdec.hip calls the bodies with the kernel's own parameter and
+// blockIdx.x; kernels_jpegdec_batch.hip first looks up the workgroup's file (jpegdec_batch.hpp) and calls them with that file's Args in
+// device memory and the index within the file.  The caller names the flag words and declares the LDS.  A body binds the Args it is
+// given and never copies them: a by-value copy sends k_jdec_sync to 392 bytes of scratch per lane (the run-time index into exit[r & 1]).
+// The per-lane arithmetic is jpegdec_core.hpp's.  profiles/jpeg_shared_bodies/ has the single-file code object before and after it was
+// built from these bodies, and the timings; tests/test_gpu_jpegdec_batch.py holds batch and single call to each other sample for sample,
+// report for report.  Device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "host_util.hpp"
 #include "jpeg_launch.hpp"
 #include "jpegdec_batch.hpp"
 #include "jpegdec_core.hpp"
@@ -52,11 +53,6 @@ struct Layout {
     size_t bytes;                                                                        // up_bytes + work_bytes
     uint32_t pieces;
 };
-
-inline size_t align256(size_t n)
-{
-    return (n + 255) & ~(size_t)255;
-}
 
 inline Layout layout_of(const Parsed& ps, uint32_t nsub)
 {

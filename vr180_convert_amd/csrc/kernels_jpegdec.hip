@@ -1,9 +1,11 @@
-// kernels_jpegdec.hip -- the device JPEG decoder's kernels: unstuffing of the scan (count, place); the rounds of self-synchronising
-// Huffman decoding, one lane per subsequence (init, sync); the last pass from the converged entry states into coefficients (write);
-// the DC differences gathered by component for their scan (dcgather); dequantisation and inverse DCT into padded component planes
-// (idct); chroma upsampling, colour conversion and the store of BGR rows (colour).  The exclusive scans between them are the
-// encoder's (kernels_jpeg.hip: launch_scan).  INTEGRATION.md section 8 has the contract, DESIGN.md section 14 the design.  A code
-// object of its own: work that decodes nothing does not load it.
+// kernels_jpegdec.hip -- the device JPEG decoder's kernels for one file: unstuffing of the scan (count, place); the rounds of
+// self-synchronising Huffman decoding, one lane per subsequence (init, sync); the last pass from the converged entry states into
+// coefficients (write); the DC differences gathered by component for their scan (dcgather); dequantisation and inverse DCT into padded
+// component planes (idct); chroma upsampling, colour conversion and the store of BGR rows (colour).  What a workgroup of each does is
+// written once, in jpegdec_kernels.hpp, for these kernels and for the batch's (kernels_jpegdec_batch.hip); here are the kernels'
+// names, their LDS and their launchers.  The exclusive scans between them are the encoder's (kernels_jpeg.hip: launch_scan).
+// INTEGRATION.md section 8 has the contract, DESIGN.md section 14 the design.  A code object of its own: work that decodes nothing does
+// not load it.
 //
 // Nothing waits on another workgroup, and every loop is bounded: the symbol loops by the bits of one subsequence, the code-length loop
 // by 16, the segment search by 32 halvings.  Rounds are launches; the host reads flags[] between them.  Wrong entry states are part
@@ -11,275 +13,62 @@
 // last pass writes only blocks below its segment's quota.
 #include <hip/hip_runtime.h>
 
-#include "jpegdec_launch.hpp"
+#include "jpegdec_kernels.hpp"
 
 namespace v1c {
 namespace jpegdec {
 
-namespace {
+// Each kernel is its stage's body (jpegdec_kernels.hpp) at workgroup blockIdx.x, over the Args it was launched with.  The body takes
+// the kernel's own parameter by reference; a copy of it into a local is what sends the Huffman kernels to scratch.
 
-constexpr int kTableWords = (int)(8 * sizeof(Table) / 4);
-
-// the eight Huffman tables into LDS (Tables: dc[4] and ac[4] lie back to back)
-__device__ inline void load_tables(Table* t, const Tables* src, int tid)
-{
-    const uint32_t* s = (const uint32_t*)&src->dc[0];
-    uint32_t* d = (uint32_t*)t;
-    for (int i = tid; i < kTableWords; i += 256)
-        d[i] = s[i];
-}
-
-__device__ inline TablePair pair_of(const Geom& g, const Table* t)
-{
-    TablePair tp{t, t + 4, 0, 0};
-    const uint32_t cd = g.td[1] | g.td[2] << 4, ca = g.ta[1] | g.ta[2] << 4;  // chroma: the blocks behind the ny luma ones
-    for (uint32_t c = 0; c < 4; c++) {
-        tp.dcsel |= (c < g.ny ? (uint32_t)g.td[0] : 0u) << (4 * c);
-        tp.acsel |= (c < g.ny ? (uint32_t)g.ta[0] : 0u) << (4 * c);
-    }
-    if (g.nc == 3) {
-        tp.dcsel |= cd << (4 * g.ny);
-        tp.acsel |= ca << (4 * g.ny);
-    }
-    return tp;
-}
-
-struct Sub {
-    uint32_t k, start, end, E;  // segment; first bit, end bit, the segment's end bit
-    bool first, last;           // of its segment
-};
-
-__device__ inline Sub sub_of(const Args& a, uint32_t i)
-{
-    uint32_t lo = 0, hi = a.g.nseg - 1;
-    for (int it = 0; it < 32 && lo < hi; it++) {  // the last k with subfirst[k] <= i
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (a.subfirst[mid] <= i)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    Sub s;
-    s.k = lo;
-    s.E = 8 * a.segoff[lo + 1];
-    const uint32_t j = i - a.subfirst[lo];
-    s.start = 8 * a.segoff[lo] + j * a.S;
-    s.end = min(s.start + a.S, s.E);
-    s.first = j == 0;
-    s.last = i + 1 == a.subfirst[lo + 1];
-    return s;
-}
-
-}  // namespace
-
-// 1: the bytes every piece of the stuffed scan drops
 __global__ __launch_bounds__(256) void k_jdec_count(Args a)
 {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= a.pieces)
-        return;
-    const uint4 v = ((const uint4*)a.scan)[p];
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    uint32_t prev = p ? a.scan[(size_t)p * kPiece - 1] : 0u, n = 0;
-    const uint32_t after = a.scan[(size_t)p * kPiece + kPiece];
-#pragma unroll
-    for (int j = 0; j < kPiece; j++) {
-        const uint32_t cur = (w[j >> 2] >> ((j & 3) * 8)) & 255u;
-        const uint32_t next = j + 1 < kPiece ? (w[(j + 1) >> 2] >> (((j + 1) & 3) * 8)) & 255u : after;
-        n += (p * kPiece + j < a.scan_len && dropped(prev, cur, next)) ? 1u : 0u;
-        prev = cur;
-    }
-    a.drop[p] = n;
+    count_body(a, blockIdx.x);
 }
 
-// 2: every kept byte at its place in the unstuffed stream
 __global__ __launch_bounds__(256) void k_jdec_place(Args a)
 {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= a.pieces)
-        return;
-    const uint4 v = ((const uint4*)a.scan)[p];
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    uint32_t prev = p ? a.scan[(size_t)p * kPiece - 1] : 0u;
-    const uint32_t after = a.scan[(size_t)p * kPiece + kPiece];
-    uint8_t* dst = (uint8_t*)a.u + ((uint64_t)p * kPiece - a.dropoff[p]);  // (at most the piece's own offset: inside a.u)
-#pragma unroll
-    for (int j = 0; j < kPiece; j++) {
-        const uint32_t cur = (w[j >> 2] >> ((j & 3) * 8)) & 255u;
-        const uint32_t next = j + 1 < kPiece ? (w[(j + 1) >> 2] >> (((j + 1) & 3) * 8)) & 255u : after;
-        if (p * kPiece + j < a.scan_len && !dropped(prev, cur, next))
-            *dst++ = (uint8_t)cur;
-        prev = cur;
-    }
+    place_body(a, blockIdx.x);
 }
 
-// 3: before the first round: what F_i "gave" is the grid state of the subsequence behind it, and no entry state was computed for
 __global__ __launch_bounds__(256) void k_jdec_init(Args a)
 {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= a.nsub)
-        return;
-    const Sub s = sub_of(a, i);
-    a.exit[0][i] = State{s.end, 0u};
-    a.last[i] = State{0xffffffffu, 0xffffffffu};
-    a.count[i] = 0;
+    init_body(a, blockIdx.x);
 }
 
-// 4: one round.  A lane whose entry state is the one it last computed for passes its result on; the others run F_i.  A changed entry
-// state of any subsequence raises this round's flag.
+// Round r raises flags[r & 1] and clears flags[(r + 1) & 1], the next round's; the host reads them between the launches.
 __global__ __launch_bounds__(256) void k_jdec_sync(Args a, uint32_t r)
 {
     __shared__ Table t[8];
     load_tables(t, a.tab, threadIdx.x);
     __syncthreads();
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i == 0)
-        a.flags[(r + 1) & 1u] = 0;  // (the next round's; nobody reads or raises it before this kernel has ended)
-    if (i >= a.nsub)
-        return;
-    const State *in = a.exit[(r - 1) & 1u];
-    State* out = a.exit[r & 1u];
-    const Sub s = sub_of(a, i);
-    const State e = s.first ? State{s.start, 0u} : in[i - 1];
-    const State was = in[i];
-    if (e == a.last[i]) {
-        out[i] = was;
-        return;
-    }
-    State x = e;
-    const uint32_t n = decode_span<false>(a.u, pair_of(a.g, t), a.g.bpm, x, s.end, s.E, nullptr, 0, 0, nullptr);
-    a.last[i] = e;
-    a.count[i] = n;
-    out[i] = x;
-    if (!s.last && !(x == was))
-        a.flags[r & 1u] = 1;
+    sync_body(a, blockIdx.x, r, t, &a.flags[r & 1u], &a.flags[(r + 1) & 1u]);
 }
 
-// 5: the last pass: every subsequence from its true entry state into the coefficients, the DC still a difference.  Only this pass
-// judges the stream: an invalid code, a run past 63, a symbol past the segment's end, a segment whose blocks are not the geometry's.
 __global__ __launch_bounds__(256) void k_jdec_write(Args a, uint32_t r)
 {
     __shared__ Table t[8];
     load_tables(t, a.tab, threadIdx.x);
     __syncthreads();
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= a.nsub)
-        return;
-    const State* fin = a.exit[r & 1u];
-    const Sub s = sub_of(a, i);
-    State e = s.first ? State{s.start, 0u} : fin[i - 1];
-    const uint32_t i0 = a.subfirst[s.k], b0 = s.k * a.g.ibl, bq = min(b0 + a.g.ibl, a.g.nblocks);
-    const uint64_t done = a.first[i] - a.first[i0];
-    const uint32_t b = done < bq - b0 ? b0 + (uint32_t)done : bq;
-    uint32_t err = kNoError;
-    decode_span<true>(a.u, pair_of(a.g, t), a.g.bpm, e, s.end, s.E, a.coef, b, bq, &err);
-    if (s.first && a.first[a.subfirst[s.k + 1]] - a.first[i0] != bq - b0)
-        err = min(err, s.start);
-    if (err != kNoError)
-        atomicMin(&a.flags[2], err);
+    write_body(a, blockIdx.x, r, t, &a.flags[2]);
 }
 
-// 6: the DC differences in the order their scan runs over: all blocks of Y, of Cb, of Cr
 __global__ __launch_bounds__(256) void k_jdec_dcgather(Args a)
 {
-    const uint32_t b = blockIdx.x * 256u + threadIdx.x;
-    if (b >= a.g.nblocks)
-        return;
-    uint32_t pos, pos0;
-    dc_pos(a.g, b, pos, pos0);
-    a.dcd[pos] = (uint32_t)(int)a.coef[(size_t)b * 64];
+    dcgather_body(a, blockIdx.x);
 }
 
-// 7: coefficients to samples.  Eight lanes per block, one column (then one row) each; 32 blocks per workgroup.
 __global__ __launch_bounds__(256) void k_jdec_idct(Args a)
 {
-    __shared__ int tile[32][8][9];  // (rows padded to 9 words: the row pass reads without bank conflicts)
+    __shared__ int tile[32][8][9];
     __shared__ __attribute__((aligned(16))) int16_t zz[32 * 64];
     __shared__ uint16_t q[4][64];
-    const int tid = threadIdx.x, blk = tid >> 3, r = tid & 7;
-    q[tid >> 6][tid & 63] = a.tab->q[tid >> 6][tid & 63];
-    const uint32_t nwords = min(32u, a.g.nblocks - blockIdx.x * 32u) * 32;
-    const uint32_t* src = (const uint32_t*)a.coef + (size_t)blockIdx.x * 1024;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const uint32_t i = k * 256 + tid;
-        if (i < nwords)
-            ((uint32_t*)zz)[i] = src[i];
-    }
-    __syncthreads();
-    const uint32_t b = blockIdx.x * 32u + (uint32_t)blk;
-    const bool active = b < a.g.nblocks;
-    BlockPos pos{};
-    int d[8];
-    if (active) {
-        pos = block_pos(a.g, b);
-        const int tq = pos.comp == 0 ? a.g.tq[0] : pos.comp == 1 ? a.g.tq[1] : a.g.tq[2];
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-            d[i] = dequantise(zz[blk * 64 + zigzag_of(i * 8 + r)], q[tq][i * 8 + r]);
-        if (r == 0) {
-            uint32_t at, at0;
-            dc_pos(a.g, b, at, at0);
-            d[0] = dequantise((int16_t)(uint32_t)(a.dcoff[at + 1] - a.dcoff[at0]), q[tq][0]);
-        }
-        idct_pass<11>(d);
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-            tile[blk][i][r] = d[i];
-    }
-    __syncthreads();
-    if (active) {
-#pragma unroll
-        for (int c = 0; c < 8; c++)
-            d[c] = tile[blk][r][c];
-        idct_pass<18>(d);
-        uint2 v;
-        v.x = (uint32_t)clamp255(d[0] + 128) | (uint32_t)clamp255(d[1] + 128) << 8 | (uint32_t)clamp255(d[2] + 128) << 16 |
-              (uint32_t)clamp255(d[3] + 128) << 24;
-        v.y = (uint32_t)clamp255(d[4] + 128) | (uint32_t)clamp255(d[5] + 128) << 8 | (uint32_t)clamp255(d[6] + 128) << 16 |
-              (uint32_t)clamp255(d[7] + 128) << 24;
-        uint8_t* plane = pos.comp == 0 ? a.plane[0] : pos.comp == 1 ? a.plane[1] : a.plane[2];
-        *(uint2*)(plane + (size_t)(pos.y0 + r) * plane_pitch(a.g, pos.comp) + pos.x0) = v;  // (planes, pitches and x0: multiples of 8)
-    }
+    idct_body(a, blockIdx.x, tile, zz, q);
 }
 
-// 8: four pixels of a row per lane: luma, upsampled chroma, B G R
 __global__ __launch_bounds__(256) void k_jdec_colour(Args a)
 {
-    const uint32_t wq = (a.g.w + 3) / 4;
-    const uint64_t idx = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (idx >= (uint64_t)wq * a.g.h)
-        return;
-    const uint32_t y = (uint32_t)(idx / wq), x0 = (uint32_t)(idx - (uint64_t)y * wq) * 4;
-    const uint32_t n = min(4u, a.g.w - x0), py = plane_pitch(a.g, 0), pc = plane_pitch(a.g, 1);
-    uint8_t px[12];
-#pragma unroll
-    for (uint32_t j = 0; j < 4; j++) {
-        const uint32_t x = min(x0 + j, a.g.w - 1);
-        const int lum = a.plane[0][(size_t)y * py + x];
-        if (a.g.nc == 1) {
-            if (a.out_cn == 1)
-                px[j] = (uint8_t)lum;
-            else
-                px[3 * j] = px[3 * j + 1] = px[3 * j + 2] = (uint8_t)lum;
-        } else {
-            ycc_to_bgr(lum, chroma_sample(a.plane[1], pc, a.g, x, y), chroma_sample(a.plane[2], pc, a.g, x, y), px + 3 * j);
-        }
-    }
-    uint8_t* dst = a.out + (int64_t)y * a.pitch + (int64_t)x0 * a.out_cn;
-    const uint32_t nbytes = n * a.out_cn;
-    if (n == 4 && ((uintptr_t)dst & 3u) == 0) {
-        uint32_t* d4 = (uint32_t*)dst;
-#pragma unroll
-        for (uint32_t k = 0; k < 3; k++)
-            if (k * 4 < nbytes)
-                d4[k] = (uint32_t)px[4 * k] | (uint32_t)px[4 * k + 1] << 8 | (uint32_t)px[4 * k + 2] << 16 | (uint32_t)px[4 * k + 3] << 24;
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < 12; k++)
-            if (k < nbytes)
-                dst[k] = px[k];
-    }
+    colour_body(a, blockIdx.x);
 }
 
 namespace {

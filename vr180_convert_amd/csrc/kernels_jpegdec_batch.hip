@@ -1,8 +1,8 @@
 // kernels_jpegdec_batch.hip -- the device JPEG decoder's kernels for a batch of files (v1c_jpeg_decode_batch): the eight kernels of
 // kernels_jpegdec.hip over a flat work list.  A workgroup finds its file by a bounded binary search over the first workgroups of the
 // files (file_of, jpegdec_batch.hpp), takes that file's Args from a device array and does what the single-file kernel's workgroup of the
-// same index within the file does: the bodies in jpegdec_kernels.hpp are those kernels' line for line.  The file is uniform per
-// workgroup, so the Huffman tables are staged in LDS once per workgroup as there.  DESIGN.md section 15 has the design.
+// same index within the file does: both call the same body of jpegdec_kernels.hpp.  The file is uniform per workgroup, so the Huffman
+// tables are staged in LDS once per workgroup as there.  DESIGN.md section 15 has the design.
 //
 // Nothing waits on another workgroup; every loop is bounded (the bodies' loops, and the file search by 32 halvings).  A file rests
 // from the round after its first quiet one (file_active): its workgroups return before they touch a table or a state.

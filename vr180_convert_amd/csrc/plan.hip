@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/vr180_remap.h"
+#include "host_util.hpp"
 #include "kernels.hpp"
 #include "radial_fit.hpp"
 
@@ -37,7 +38,7 @@ static int fail(int code, const std::string& msg)
     return code;
 }
 
-// the same for the entry points of other files (feat.hip)
+// the same for the entry points of other files (host_util.hpp)
 namespace v1c {
 int set_error(int code, const std::string& msg)
 {
@@ -51,22 +52,6 @@ int set_error(int code, const std::string& msg)
         if (_e != hipSuccess)                                                                           \
             return fail(V1C_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));                  \
     } while (0)
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess)
-            prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
 
 // ------------------------------------------------------------------------------------------
 // OpenCV's fixed-point interpolation table (initInterTab2D, imgwarp.cpp)

@@ -7,52 +7,12 @@
 #include <vector>
 
 #include "../../include/vr180_remap.h"
+#include "host_util.hpp"
 #include "png_host.hpp"
 #include "png_launch.hpp"
 
-namespace v1c {
-int set_error(int code, const std::string& msg);  // plan.hip: the message v1c_last_error returns
-}
-
 using namespace v1c;
 using namespace v1c::png;
-
-namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess)
-            prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0)
-            (void)hipSetDevice(prev);
-    }
-};
-
-size_t align256(size_t n)
-{
-    return (n + 255) & ~(size_t)255;
-}
-
-// the stream-ordered workspace of one call, released on every way out
-struct Workspace {
-    uint8_t* p = nullptr;
-    hipStream_t st;
-    explicit Workspace(hipStream_t s) : st(s) {}
-    ~Workspace()
-    {
-        if (p)
-            (void)hipFreeAsync(p, st);
-    }
-};
-
-}  // namespace
 
 extern "C" uint64_t v1c_png_bound(int h, int w, int cn, int depth, int band_rows)
 {
