@@ -439,6 +439,47 @@ typedef struct v1c_jpeg_image {       /* one image of a batch; every field as th
 } v1c_jpeg_image;
 int v1c_jpeg_encode_batch(int device, void* stream, int n, v1c_jpeg_image* images, uint64_t workspace_budget, uint32_t* chunks_out);
 
+/* ---- Optimised Huffman tables (INTEGRATION.md section 7 states the procedure; tests/jpg_opt_ref.py restates it) -------------------
+ * The same file with Huffman tables built for the image -- its symbols are counted on the device, then libjpeg's
+ * jpeg_gen_optimal_table procedure runs there on the counts -- in place of the Annex K tables: the same coefficients, a smaller scan
+ * and a smaller DHT segment.  The entries above do not change with it.  v1c_jpeg_bound holds for the optimised scan too: a DC table
+ * has at most 13 leaves, so a DC code is at most 12 bits and a block at most 23 + 63 * 26 bits, within the 208 bytes of the bound.   */
+#define V1C_JPEG_DHT_MAX (4 * (1 + 16 + 256)) /* bytes of the DHT segment's body: per table Tc << 4 | Th, BITS, HUFFVAL            */
+#define V1C_JPEG_HEADER_OPT_MAX 2048          /* bytes v1c_jpeg_header_opt can write                                                */
+
+/* v1c_jpeg_header with the DHT body of v1c_jpeg_encode_opt / v1c_jpeg_encode_batch_opt (`dht`, dht_size <= V1C_JPEG_DHT_MAX bytes:
+ * the two tables of a cn = 1 image or the four of a colour image) in place of the Annex K tables.  Host-only.  Returns the number
+ * of bytes, or V1C_E_INVALID (also for a body that is not whole tables in the segment's order).                                      */
+int64_t v1c_jpeg_header_opt(int h, int w, int cn, int quality, int subsampling, int restart_mcus, const uint8_t* dht, uint32_t dht_size,
+                            uint8_t* out, uint64_t capacity);
+
+/* v1c_jpeg_encode with optimised tables: the scan in out_host (capacity >= v1c_jpeg_bound), its size in *size_out, and the DHT
+ * segment's body in dht_out (HOST memory of V1C_JPEG_DHT_MAX bytes) with its size in *dht_size_out, for v1c_jpeg_header_opt.  The
+ * tables are built on the device between two kernels of the chain, and their record comes to the host in the copy of the size: the
+ * call SYNCHRONISES the stream twice, as v1c_jpeg_encode does.  Arguments are checked as there; V1C_E_UNSUPPORTED while `stream`
+ * is being captured into a graph.                                                                                                   */
+int v1c_jpeg_encode_opt(int device, void* stream, const void* img, int h, int w, int64_t pitch, int cn, int quality, int subsampling,
+                        int restart_mcus, uint8_t* out_host, uint64_t capacity, uint64_t* size_out, uint8_t* dht_out,
+                        uint32_t* dht_size_out);
+
+/* v1c_jpeg_encode_batch with optimised tables per image: an image with optimize != 0 gets, byte for byte, the scan and the DHT body
+ * of v1c_jpeg_encode_opt, one with optimize == 0 the scan of v1c_jpeg_encode (dht_size 0).  The chunk's upload holds one set of
+ * tables per distinct quality of the plain images and one per optimising image; every chunk still synchronises TWICE: the records
+ * of all its tables come with its sizes.  Everything else as v1c_jpeg_encode_batch.                                               */
+typedef struct v1c_jpeg_image_opt {   /* one image of a batch; the fields of v1c_jpeg_image, then:                                */
+    const void* img;
+    int h, w;
+    int64_t pitch;
+    int cn, quality, subsampling, restart_mcus;
+    uint8_t* out_host;
+    uint64_t capacity;
+    uint64_t size;
+    int optimize;                     /* != 0: tables of its own                                                                 */
+    uint32_t dht_size;                /* out: bytes of dht, 0 for optimize == 0                                                  */
+    uint8_t dht[V1C_JPEG_DHT_MAX];    /* out: the DHT segment's body                                                             */
+} v1c_jpeg_image_opt;
+int v1c_jpeg_encode_batch_opt(int device, void* stream, int n, v1c_jpeg_image_opt* images, uint64_t workspace_budget, uint32_t* chunks_out);
+
 /* ---- JPEG decoding into a device image (INTEGRATION.md section 8 states the contract; tests/jpgdec_ref.py restates it) ------------
  * Sequential DCT with Huffman coding and 8-bit samples (SOF0, SOF1) in one interleaved scan: one component, or three as JFIF YCbCr
  * in 4:4:4, 4:2:2 or 4:2:0; any DQT, DHT and DRI.  Everything else a JPEG file may be -- progressive, lossless, arithmetic, 12-bit,

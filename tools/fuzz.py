@@ -7,7 +7,7 @@ and destination views (dword-aligned or not), per-unit rotations, apply_lr pairs
 (v1c_remap_lut) on random float32 maps sprinkled with NaN, infinities, 2^15 / 2^26 / 2^31-scale values and ties of the 1/32 grid.
 
     python3 tools/fuzz.py [--seconds 300] [--seed 1] [--big 0.15] [--lut 0.15] [--hot 0.3] [--gen2 0] [--api 0.1] [--auto 0.06] [--fused 0.06] [--log gpurun_out/fuzz.log]
-                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--cases N]
+                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--cases N]
 
 --wide P: that share of the cases has uint16 or float32 pixels (k_remap_wide): the chain cases above -- same grammar, views, batches, pairs,
 per-unit rotations, graph replays and the same three masks, counted in the same counters -- and the LUT cases (v1c_remap_lut_ex, nothing left
@@ -19,7 +19,7 @@ towards the run's case total (the summary line says how many).  --png P: that sh
 kernels' 64-lane steps, 256-byte segments and 64-segment groups, noise, Fibonacci frequencies; gray / BGR / BGRA, 8- and 16-bit) in a random
 view with a random band height and either filter -- against tests/png_ref.py's file, byte for byte.  --jpeg P: that share goes through the device JPEG encoder (encode_jpeg_tensor) -- a remap result or a
 random image in a random view, any quality, either subsampling, a random restart interval -- against tests/jpg_ref.py's file, byte for
-byte.  --jpegbatch P: that share goes through the batched device JPEG encoder (encode_jpeg_tensors) -- lists of 1 to 12 random images up to 96 x 96, each with its own parameters -- against the single calls and tests/jpg_ref.py.  --jpegdec P: that share goes through the device JPEG decoder (decode_jpeg_tensor) -- a random image up to 96 x 96 written by Pillow or
+byte.  --jpegbatch P: that share goes through the batched device JPEG encoder (encode_jpeg_tensors) -- lists of 1 to 12 random images up to 96 x 96, each with its own parameters -- against the single calls and tests/jpg_ref.py.  --jpegopt P: that share goes through the device JPEG encoder with optimised Huffman tables (optimize=True) -- lists of 1 to 8 random images up to 160 x 160 that mix optimising and plain images -- against tests/jpg_opt_ref.py and the single calls.  --jpegdec P: that share goes through the device JPEG decoder (decode_jpeg_tensor) -- a random image up to 96 x 96 written by Pillow or
 by tests/jpg_ref.py with random sampling, quality, restart setting and optimised tables, at a random subsequence size -- against
 tests/jpgdec_ref.py's pixels, byte for byte.  --feat P: that share goes through the feature
 pipeline of --automatch devfm (features.detect / features.match) against tests/feat_ref.py, keypoints, descriptors and matches equal: images of
@@ -880,6 +880,62 @@ def jpegbatch_case(rng, dev) -> tuple[str, int]:
     return f"JPEG batch n={n} budget={budget!r} chunks={chunks} quality={quality} subsampling={subs} restart_mcus={restarts!r} {' '.join(kinds)}", bad
 
 
+def jpegopt_case(rng, dev) -> tuple[str, int]:
+    """the optimised Huffman tables of the device JPEG encoder (optimize=True) against the restatement (jpg_opt_ref.encode) and, for a
+    list, against the single calls, every file byte for byte: 1 to 8 random images up to 160 x 160 -- smooth, noise, flat, hard edges,
+    mixed, flat with a noise patch; gray / BGR / BGRA -- in random views, each with its own quality, subsampling and restart interval
+    and its own choice of optimised or standard tables; now and then under a workspace budget that cuts the list into chunks.  Every
+    optimised file must decode (Pillow) to the pixels of its standard-table file and not be larger than it by more than nothing: the
+    scan may tie for a tiny image, the DHT segment always shrinks."""
+    import jpg_cases as JC
+    import jpg_opt_ref as JO
+    import jpg_ref as JR
+
+    n = int(rng.integers(1, 9))
+    imgs, ts, quality, subs, restarts, opts, kinds = [], [], [], [], [], [], []
+    for _ in range(n):
+        h, w = (int(v) for v in (rng.integers(1, 25, 2) if rng.random() < 0.4 else rng.integers(1, 161, 2)))
+        cn = int(rng.choice([3, 3, 1, 4]))
+        kind = str(rng.choice(["smooth", "noise", "flat", "edges", "mixed", "patch"]))
+        seed = int(rng.integers(0, 1 << 30))
+        if kind == "smooth":
+            img = JC.smooth(h, w, cn, seed)
+        elif kind == "noise":
+            img = JC.noise(h, w, cn, seed)
+        elif kind == "flat":
+            img = np.full((h, w, cn), int(rng.integers(0, 256)), np.uint8)
+        elif kind == "edges":
+            img = (JC.noise((h + 7) // 8, (w + 7) // 8, cn, seed) > 127).astype(np.uint8).repeat(8, 0).repeat(8, 1)[:h, :w] * 255
+        elif kind == "patch":
+            img = np.full((h, w, cn), int(rng.integers(0, 256)), np.uint8)
+            img[: (h + 3) // 4, : (w + 3) // 4] = JC.noise((h + 3) // 4, (w + 3) // 4, cn, seed)
+        else:
+            img = np.where(JC.noise(h, w, 1, seed) > 200, JC.noise(h, w, cn, seed + 1), JC.smooth(h, w, cn, seed + 2))
+        img = np.ascontiguousarray(img)
+        sub = "420" if rng.random() < 0.6 else "444"
+        m = 16 if (cn != 1 and sub == "420") else 8
+        nmcu = -(-h // m) * -(-w // m)
+        r = rng.random()
+        imgs.append(img), ts.append(make_view(rng, img, dev, allow_unaligned=True)), kinds.append(f"{kind}{tuple(img.shape)}")
+        quality.append(int(rng.choice([1, 10, 49, 50, 75, 90, 95, 100])) if rng.random() < 0.7 else int(rng.integers(1, 101)))
+        subs.append(sub)
+        restarts.append(None if r < 0.25 else 1 if r < 0.35 else nmcu if r < 0.45 else 65535 if r < 0.5 else int(rng.integers(1, nmcu + 2)))
+        opts.append(bool(rng.random() < 0.75))
+    budget = None if rng.random() < 0.6 else int(rng.integers(1, 400_000))
+    got = V.encode_jpeg_tensors(ts, quality=quality, subsampling=subs, restart_mcus=restarts, workspace_budget=budget, optimize=opts)
+    chunks = V.last_encode_batch_report()["chunks"]
+    bad = 0 if len(got) == n and (budget is not None or chunks == 1) else 1
+    for img, t, q, sub, restart, o, g in zip(imgs, ts, quality, subs, restarts, opts, got):
+        std = JR.encode(img, q, sub, restart)
+        for want in (JO.encode(img, q, sub, restart, optimize=o), V.encode_jpeg_tensor(t, quality=q, subsampling=sub, restart_mcus=restart, optimize=o)):
+            bad += abs(len(g) - len(want)) + sum(a != b for a, b in zip(g, want)) if g != want else 0
+        if o and (len(g) >= len(std) or not np.array_equal(JR.decode(g), JR.decode(std))):
+            bad += 1
+    KINDS["jpegopt"] = KINDS.get("jpegopt", 0) + 1
+    return (f"JPEG optimize n={n} budget={budget!r} chunks={chunks} optimize={opts} quality={quality} subsampling={subs} "
+            f"restart_mcus={restarts!r} {' '.join(kinds)}"), bad
+
+
 def jpegdec_case(rng, dev) -> tuple[str, int]:
     """the device JPEG decoder (decode_jpeg_tensor) against its restatement (jpgdec_ref.decode), the pixels byte for byte: a random
     image up to 96 x 96 -- smooth, noise, flat, mixed -- written by Pillow (grey, 4:4:4, 4:2:2 or 4:2:0, any quality, optimised tables
@@ -1099,6 +1155,7 @@ def main() -> int:
     ap.add_argument("--jpeg", type=float, default=0.0, help="share of cases through the device JPEG encoder (encode_jpeg_tensor) against jpg_ref.encode")
     ap.add_argument("--jpegdec", type=float, default=0.0, help="share of cases through the device JPEG decoder (decode_jpeg_tensor) against jpgdec_ref.decode")
     ap.add_argument("--jpegbatch", type=float, default=0.0, help="share of cases through the batched device JPEG encoder (encode_jpeg_tensors) against the single calls and jpg_ref.encode")
+    ap.add_argument("--jpegopt", type=float, default=0.0, help="share of cases through the device JPEG encoder with optimised Huffman tables (optimize=True, single and batched) against jpg_opt_ref.encode")
     ap.add_argument("--cases", type=int, default=None, help="stop after this many cases (before --seconds runs out)")
     ap.add_argument("--feat", type=float, default=0.0, help="share of cases through the feature pipeline (features.detect / features.match) against tests/feat_ref.py")
     ap.add_argument("--only", type=int, default=None, help="run only this case number (reproduce)")
@@ -1133,8 +1190,10 @@ def main() -> int:
             r_kind = rng.random()
             wide_chain = False
             counted = True
-            top = 1.0 - a.jpegbatch - a.jpegdec
-            if r_kind >= 1.0 - a.jpegbatch:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+            top = 1.0 - a.jpegopt - a.jpegbatch - a.jpegdec
+            if r_kind >= 1.0 - a.jpegopt:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+                desc, bad = jpegopt_case(rng, dev)
+            elif r_kind >= 1.0 - a.jpegopt - a.jpegbatch:
                 desc, bad = jpegbatch_case(rng, dev)
             elif r_kind >= top:
                 desc, bad = jpegdec_case(rng, dev)

@@ -26,6 +26,7 @@ SYMBOLS = [
     "v1c_png_bound", "v1c_png_deflate",
     "v1c_jpeg_bound", "v1c_jpeg_header", "v1c_jpeg_encode", "v1c_jpeg_encode_batch",
     "v1c_jpeg_decode_info", "v1c_jpeg_decode", "v1c_jpeg_decode_batch",
+    "v1c_jpeg_header_opt", "v1c_jpeg_encode_opt", "v1c_jpeg_encode_batch_opt",
 ]
 
 
@@ -105,6 +106,13 @@ def lib() -> C.CDLL:
         pass
     try:
         L.v1c_jpeg_encode_batch.argtypes = [i32, vp, i32, vp, C.c_uint64, vp]
+    except AttributeError:  # (an older build behind V1C_LIB)
+        pass
+    try:
+        L.v1c_jpeg_header_opt.argtypes = [i32, i32, i32, i32, i32, i32, vp, C.c_uint32, vp, C.c_uint64]
+        L.v1c_jpeg_header_opt.restype = i64
+        L.v1c_jpeg_encode_opt.argtypes = [i32, vp, vp, i32, i32, i64, i32, i32, i32, i32, vp, C.c_uint64, vp, vp, vp]
+        L.v1c_jpeg_encode_batch_opt.argtypes = [i32, vp, i32, vp, C.c_uint64, vp]
     except AttributeError:  # (an older build behind V1C_LIB)
         pass
     L.v1c_plan_run.argtypes = [vp, vp, C.POINTER(_abi.Unit), i32]

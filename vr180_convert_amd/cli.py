@@ -222,6 +222,9 @@ def lr(
                                                                          "files are read by the host)")] = False,
     device_decode_batch: Annotated[bool, typer.Option("--device-decode-batch", help="As --device-decode, with all the files decoded in one "
                                                                                      "batch that shares its kernel launches")] = False,
+    device_jpeg_optimize: Annotated[bool, typer.Option("--device-jpeg-optimize", help="With --device-jpeg or --device-jpeg-batch: Huffman "
+                                                                                       "tables built for each image on the GPU (smaller "
+                                                                                       "files, the same pixels)")] = False,
 ) -> None:
     """Remap a pair of fisheye images to a pair of SBS equirectangular images."""
     from .remapper import apply_lr
@@ -257,7 +260,8 @@ def lr(
     apply_lr(chain, left_path=left_in, right_path=right_in, out_path=out, radius=radius_, size_output=parse_size(size),
              interpolation=interp, boarder_mode=border, boarder_value=border_value, merge=merge,
              **({"device_png": True} if device_png else {}), **({"device_jpeg": "batch"} if device_jpeg_batch else {"device_jpeg": True} if device_jpeg else {}),
-             **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}))
+             **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}),
+             **({"device_jpeg_optimize": True} if device_jpeg_optimize else {}))
 
 
 @app.command()
@@ -280,6 +284,9 @@ def s(
                                                                          "files are read by the host)")] = False,
     device_decode_batch: Annotated[bool, typer.Option("--device-decode-batch", help="As --device-decode, with all the files decoded in one "
                                                                                      "batch that shares its kernel launches")] = False,
+    device_jpeg_optimize: Annotated[bool, typer.Option("--device-jpeg-optimize", help="With --device-jpeg or --device-jpeg-batch: Huffman "
+                                                                                       "tables built for each image on the GPU (smaller "
+                                                                                       "files, the same pixels)")] = False,
 ) -> None:
     """Remap fisheye images to equirectangular images (one shared map for all of them)."""
     from .remapper import apply
@@ -296,7 +303,8 @@ def s(
           size_output=parse_size(size), interpolation=_flag(interpolation, _INTERPOLATIONS, "inter_", "interpolation"),
           boarder_mode=_flag(boarder_mode, _BORDERS, "border_", "border mode"), boarder_value=boarder_value,
           **({"device_png": True} if device_png else {}), **({"device_jpeg": "batch"} if device_jpeg_batch else {"device_jpeg": True} if device_jpeg else {}),
-          **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}))
+          **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}),
+          **({"device_jpeg_optimize": True} if device_jpeg_optimize else {}))
 
 
 @app.command()

@@ -210,5 +210,23 @@ __host__ __device__ inline void encode_block(const ZZ& zz, int pred, const uint3
         emit(ac[0] & 0xffffu, (int)(ac[0] >> 16));
 }
 
+// The symbols encode_block codes for a block, for the optimised tables (jpeg_opt_core.hpp): the same walk over a table whose entry of
+// symbol i is the 16-bit code i (identity_entry), so that every token carries its symbol in front of its amplitude.  Calls
+// count(is_dc, symbol) once per token: the DC category, every ZRL (0xF0), every run / size symbol, and EOB (0) where encode_block emits it.
+__host__ __device__ inline uint32_t identity_entry(int symbol)
+{
+    return (16u << 16) | (uint32_t)symbol;
+}
+
+template <class ZZ, class Count>
+__host__ __device__ inline void block_symbols(const ZZ& zz, int pred, const uint32_t* identity, Count&& count)
+{
+    bool dc = true;
+    encode_block(zz, pred, identity, identity, [&](uint32_t bits, int len) {
+        count(dc, (int)(bits >> (len - 16)));
+        dc = false;
+    });
+}
+
 }  // namespace jpeg
 }  // namespace v1c

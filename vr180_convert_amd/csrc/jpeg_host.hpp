@@ -90,8 +90,9 @@ inline void put_segment(std::vector<uint8_t>& out, int marker, const std::vector
     out.insert(out.end(), body.begin(), body.end());
 }
 
-// SOI, APP0 (JFIF 1.01, aspect 1:1), DQT, SOF0, DHT, DRI, SOS: everything in front of the scan
-inline std::vector<uint8_t> file_header(const Geom& g, int quality)
+// SOI, APP0 (JFIF 1.01, aspect 1:1), DQT, SOF0, DHT, DRI, SOS: everything in front of the scan.  dht: the DHT segment's body of an
+// optimising encode (jpeg_opt_core.hpp), or NULL for the Annex K tables
+inline std::vector<uint8_t> file_header(const Geom& g, int quality, const uint8_t* dht = nullptr, uint32_t dht_size = 0)
 {
     Tables t;
     make_tables(quality, t);
@@ -113,11 +114,13 @@ inline std::vector<uint8_t> file_header(const Geom& g, int quality)
     b.clear();
     const HuffSpec* specs[4] = {&kDcLuma, &kAcLuma, &kDcChroma, &kAcChroma};
     const uint8_t ids[4] = {0x00, 0x10, 0x01, 0x11};
-    for (uint32_t i = 0; i < (g.nc == 1 ? 2u : 4u); i++) {
+    for (uint32_t i = 0; i < (g.nc == 1 ? 2u : 4u) && !dht; i++) {
         b.push_back(ids[i]);
         b.insert(b.end(), specs[i]->bits, specs[i]->bits + 16);
         b.insert(b.end(), specs[i]->vals, specs[i]->vals + specs[i]->n);
     }
+    if (dht)
+        b.assign(dht, dht + dht_size);
     put_segment(out, 0xc4, b);
     put_segment(out, 0xdd, {(uint8_t)(g.restart >> 8), (uint8_t)g.restart});
     b = {(uint8_t)g.nc};

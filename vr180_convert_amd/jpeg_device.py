@@ -6,6 +6,11 @@ finished scan comes to the host, and the header segments (``v1c_jpeg_header``) a
 Baseline sequential JPEG with the standard tables, which every reader decodes -- not libjpeg's output byte for byte: the chroma
 rounding differs and the file carries restart markers (INTEGRATION.md section 7 has the contract and the measured sizes;
 ``tests/jpg_ref.py`` restates the file).
+
+``optimize=True`` (off by default) gives every image Huffman tables of its own, as ``IMWRITE_JPEG_OPTIMIZE`` and Pillow's
+``optimize=True`` do on the host: the symbols are counted and the tables built on the device (``v1c_jpeg_encode_opt``,
+``v1c_jpeg_encode_batch_opt``, csrc/kernels_jpeg_opt.hip) between two kernels of the same chain, so a call still synchronises twice;
+the pixels a reader decodes are the same, the file is smaller (``tests/jpg_opt_ref.py`` restates it).
 """
 from __future__ import annotations
 
@@ -20,6 +25,8 @@ from .remapper import _stream_ptr
 
 SUBSAMPLINGS = {"444": 0, "420": 2}  # V1C_JPEG_444 / V1C_JPEG_420
 HEADER_MAX = 1024                    # V1C_JPEG_HEADER_MAX
+DHT_MAX = 4 * (1 + 16 + 256)         # V1C_JPEG_DHT_MAX
+HEADER_OPT_MAX = 2048                # V1C_JPEG_HEADER_OPT_MAX
 # Bytes of page-locked memory a batch may land in at once (the sum of its images' v1c_jpeg_bound: 3.25 bytes per sample byte of a BGR
 # image in 4:2:0, so 64 results of 2048 x 2048 would pin 1.3 GB); a longer list goes to the engine in several sub-lists.
 PINNED_BUDGET = 1 << 30
@@ -29,6 +36,11 @@ class JpegImage(C.Structure):
     """``v1c_jpeg_image`` (include/vr180_remap.h)"""
     _fields_ = [("img", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("pitch", C.c_int64), ("cn", C.c_int), ("quality", C.c_int),
                 ("subsampling", C.c_int), ("restart_mcus", C.c_int), ("out_host", C.c_void_p), ("capacity", C.c_uint64), ("size", C.c_uint64)]
+
+
+class JpegImageOpt(C.Structure):
+    """``v1c_jpeg_image_opt`` (include/vr180_remap.h)"""
+    _fields_ = JpegImage._fields_ + [("optimize", C.c_int), ("dht_size", C.c_uint32), ("dht", C.c_uint8 * DHT_MAX)]
 
 
 def default_restart_mcus(height: int, width: int, channels: int, subsampling: str = "420") -> int:
@@ -90,33 +102,50 @@ def _header(h: int, w: int, cn: int, quality: int, sub: int, restart: int) -> by
     return bytes(head[:n])
 
 
-def _parts(t: torch.Tensor, quality: int, subsampling: str, restart_mcus: int | None) -> list:
+def _header_opt(h: int, w: int, cn: int, quality: int, sub: int, restart: int, dht: Any, dht_size: int) -> bytes:
+    head = (C.c_uint8 * HEADER_OPT_MAX)()
+    n = _native.lib().v1c_jpeg_header_opt(h, w, cn, quality, sub, restart, dht, dht_size, head, HEADER_OPT_MAX)
+    if n < 0:
+        _native.check(int(n), "v1c_jpeg_header_opt")
+    return bytes(head[:n])
+
+
+def _parts(t: torch.Tensor, quality: int, subsampling: str, restart_mcus: int | None, optimize: bool = False) -> list:
     t, h, w, cn, quality, sub, restart = _params(t, quality, subsampling, restart_mcus)
     lib = _native.lib()
-    head = _header(h, w, cn, quality, sub, restart)
     cap = int(lib.v1c_jpeg_bound(h, w, cn, sub, restart))
     dev = t.device
     buf = _host_buffer(dev, cap)
     size = C.c_uint64(0)
     pitch = t.stride(0) if h > 1 else w * cn
+    if optimize:
+        dht, dht_size = (C.c_uint8 * DHT_MAX)(), C.c_uint32(0)
+        rc = lib.v1c_jpeg_encode_opt(dev.index, _stream_ptr(dev), t.data_ptr(), h, w, pitch, cn, quality, sub, restart, buf.data_ptr(), buf.numel(),
+                                     C.byref(size), dht, C.byref(dht_size))
+        _native.check(rc, "v1c_jpeg_encode_opt")
+        return [_header_opt(h, w, cn, quality, sub, restart, dht, dht_size.value), buf.numpy()[:size.value], b"\xff\xd9"]
+    head = _header(h, w, cn, quality, sub, restart)
     rc = lib.v1c_jpeg_encode(dev.index, _stream_ptr(dev), t.data_ptr(), h, w, pitch, cn, quality, sub, restart, buf.data_ptr(), buf.numel(),
                              C.byref(size))
     _native.check(rc, "v1c_jpeg_encode")
     return [head, buf.numpy()[:size.value], b"\xff\xd9"]
 
 
-def encode_jpeg_tensor(t: torch.Tensor, *, quality: int = 95, subsampling: str = "420", restart_mcus: int | None = None) -> bytes:
+def encode_jpeg_tensor(t: torch.Tensor, *, quality: int = 95, subsampling: str = "420", restart_mcus: int | None = None,
+                       optimize: bool = False) -> bytes:
     """JPEG bytes of a CUDA ``uint8`` tensor ``(H, W[, C])`` in cv2 channel order (C 1: greyscale, 3: YCbCr, 4: alpha dropped), encoded
     on the device on the current stream.  ``quality``: 1 ... 100, the IJG rule (95: the host writer's).  ``subsampling``: ``"420"``
     (cv2's and Pillow's at that quality) or ``"444"``.  ``restart_mcus``: MCUs per restart interval, 1 ... 65535
-    (``default_restart_mcus``: one MCU row).  Two calls give identical bytes."""
-    return b"".join(bytes(p) for p in _parts(t, quality, subsampling, restart_mcus))
+    (``default_restart_mcus``: one MCU row).  ``optimize``: Huffman tables built for this image on the device in place of the Annex K
+    tables (a smaller file of the same pixels; the call still synchronises twice).  Two calls give identical bytes."""
+    return b"".join(bytes(p) for p in _parts(t, quality, subsampling, restart_mcus, bool(optimize)))
 
 
-def imwrite_jpeg_tensor(path: Any, t: torch.Tensor, *, quality: int = 95, subsampling: str = "420", restart_mcus: int | None = None) -> None:
+def imwrite_jpeg_tensor(path: Any, t: torch.Tensor, *, quality: int = 95, subsampling: str = "420", restart_mcus: int | None = None,
+                        optimize: bool = False) -> None:
     """``encode_jpeg_tensor`` into a file (the scan goes from the page-locked buffer to the file without a copy in between)"""
     with open(path, "wb") as f:
-        for part in _parts(t, quality, subsampling, restart_mcus):
+        for part in _parts(t, quality, subsampling, restart_mcus, bool(optimize)):
             f.write(part)
 
 
@@ -152,11 +181,13 @@ def sub_lists(bounds: Sequence[int], budget: int | None = None) -> list[tuple[in
     return out
 
 
-def _batch_parts(tensors: Sequence[torch.Tensor], quality: Any, subsampling: Any, restart_mcus: Any, workspace_budget: int | None):
+def _batch_parts(tensors: Sequence[torch.Tensor], quality: Any, subsampling: Any, restart_mcus: Any, workspace_budget: int | None,
+                 optimize: Any = False):
     """yields (index, [header, scan, EOI]) of every image, sub-list by sub-list; a scan is a view of the page-locked buffer that holds
     until the next sub-list is encoded"""
     n = len(tensors)
     qs, ss, rs = _per_image(quality, n, "quality"), _per_image(subsampling, n, "subsampling"), _per_image(restart_mcus, n, "restart_mcus")
+    opts = [bool(o) for o in _per_image(optimize, n, "optimize")]
     _last_encode_batch["chunks"], _last_encode_batch["sizes"] = 0, []
     if n == 0:
         return
@@ -172,46 +203,53 @@ def _batch_parts(tensors: Sequence[torch.Tensor], quality: Any, subsampling: Any
     sizes = []
     for lo, hi in sub_lists(bounds):
         buf = _host_buffer(dev, sum(bounds[lo:hi]))
-        images = (JpegImage * (hi - lo))()
+        # a sub-list without an optimising image goes to the entry it went to before there was the option
+        some = any(opts[lo:hi])
+        images = ((JpegImageOpt if some else JpegImage) * (hi - lo))()
         at = 0
         for k in range(lo, hi):
             t, h, w, cn, q, sub, restart = params[k]
-            images[k - lo] = JpegImage(t.data_ptr(), h, w, t.stride(0) if h > 1 else w * cn, cn, q, sub, restart, buf.data_ptr() + at, bounds[k], 0)
+            fields = (t.data_ptr(), h, w, t.stride(0) if h > 1 else w * cn, cn, q, sub, restart, buf.data_ptr() + at, bounds[k], 0)
+            images[k - lo] = JpegImageOpt(*fields, int(opts[k])) if some else JpegImage(*fields)
             at += bounds[k]
         chunks = C.c_uint32(0)
-        rc = lib.v1c_jpeg_encode_batch(dev.index, _stream_ptr(dev), hi - lo, images, int(workspace_budget or 0), C.byref(chunks))
-        _native.check(rc, "v1c_jpeg_encode_batch")
+        entry = "v1c_jpeg_encode_batch_opt" if some else "v1c_jpeg_encode_batch"
+        rc = getattr(lib, entry)(dev.index, _stream_ptr(dev), hi - lo, images, int(workspace_budget or 0), C.byref(chunks))
+        _native.check(rc, entry)
         _last_encode_batch["chunks"] += chunks.value
         host, at = buf.numpy(), 0
         for k in range(lo, hi):
             _, h, w, cn, q, sub, restart = params[k]
             size = int(images[k - lo].size)
             sizes.append(size)
-            yield k, [_header(h, w, cn, q, sub, restart), host[at:at + size], b"\xff\xd9"]
+            head = (_header_opt(h, w, cn, q, sub, restart, images[k - lo].dht, int(images[k - lo].dht_size)) if opts[k]
+                    else _header(h, w, cn, q, sub, restart))
+            yield k, [head, host[at:at + size], b"\xff\xd9"]
             at += bounds[k]
     _last_encode_batch["sizes"] = sizes
 
 
 def encode_jpeg_tensors(tensors: Sequence[torch.Tensor], *, quality: Any = 95, subsampling: Any = "420", restart_mcus: Any = None,
-                        workspace_budget: int | None = None) -> list[bytes]:
+                        workspace_budget: int | None = None, optimize: Any = False) -> list[bytes]:
     """``encode_jpeg_tensor`` of every tensor of a list in shared launches (``v1c_jpeg_encode_batch``, csrc/kernels_jpeg_batch.hip): every
-    file is byte for byte the single call's.  ``quality``, ``subsampling`` and ``restart_mcus`` are each one value for all images or a
-    sequence of the list's length; the images may differ in size and channels but lie on one device; runs on the current stream.  The
+    file is byte for byte the single call's.  ``quality``, ``subsampling``, ``restart_mcus`` and ``optimize`` are each one value for all
+    images or a sequence of the list's length (a list may mix optimising and plain images; the count of synchronisations does not
+    change with it); the images may differ in size and channels but lie on one device; runs on the current stream.  The
     engine cuts the list into chunks of at most ``workspace_budget`` bytes of device workspace (``None``: 1 GiB), each of which
     synchronises twice; a list whose summed ``v1c_jpeg_bound`` passes ``PINNED_BUDGET`` goes to the engine in several sub-lists
     (``sub_lists``), which multiplies that count a second time.  ``last_encode_batch_report()`` tells what ran."""
     out: list[bytes] = [b""] * len(tensors)
-    for k, parts in _batch_parts(tensors, quality, subsampling, restart_mcus, workspace_budget):
+    for k, parts in _batch_parts(tensors, quality, subsampling, restart_mcus, workspace_budget, optimize):
         out[k] = b"".join(bytes(p) for p in parts)
     return out
 
 
 def imwrite_jpeg_tensors(paths: Sequence[Any], tensors: Sequence[torch.Tensor], *, quality: Any = 95, subsampling: Any = "420",
-                         restart_mcus: Any = None, workspace_budget: int | None = None) -> None:
+                         restart_mcus: Any = None, workspace_budget: int | None = None, optimize: Any = False) -> None:
     """``encode_jpeg_tensors`` into files (every scan goes from the page-locked buffer to its file without a copy in between)"""
     if len(paths) != len(tensors):
         raise ValueError(f"{len(paths)} paths for {len(tensors)} images")
-    for k, parts in _batch_parts(tensors, quality, subsampling, restart_mcus, workspace_budget):
+    for k, parts in _batch_parts(tensors, quality, subsampling, restart_mcus, workspace_budget, optimize):
         with open(paths[k], "wb") as f:
             for part in parts:
                 f.write(part)

@@ -708,6 +708,7 @@ def apply(
     device_png: bool = False,
     device_jpeg: bool | Literal["batch"] = False,
     device_decode: bool | Literal["batch"] = False,
+    device_jpeg_optimize: bool = False,
 ) -> Sequence[NDArray[np.uint8]]:
     """Apply transformer to images (reference remapper.py:324-403).
 
@@ -724,8 +725,11 @@ def apply(
     ``device_jpeg=True``: every ``.jpg`` / ``.jpeg`` result that is a uint8 tensor on the device is encoded there, one call of the
     encoder per result (jpeg_device.imwrite_jpeg_tensor).  ``device_jpeg="batch"``: all of them in ONE call that shares its launches
     and its two synchronisations (jpeg_device.imwrite_jpeg_tensors); the files are the same bytes.  The other results take the paths
-    they take without it (``device_png``, the host writer)."""
+    they take without it (``device_png``, the host writer).  ``device_jpeg_optimize=True``: those files get Huffman tables built for
+    each image on the device (``optimize=True`` of jpeg_device.py: smaller files, the same pixels) with either ``device_jpeg`` mode;
+    it does nothing without one."""
     device_jpeg = _device_jpeg_mode(device_jpeg)
+    jpeg_kw = {"optimize": True} if device_jpeg_optimize else {}
     in_paths_ = [in_paths] if isinstance(in_paths, (str, Path, np.ndarray, torch.Tensor)) else in_paths
     out_paths_ = [out_paths] if isinstance(out_paths, (str, Path)) else out_paths
     del in_paths, out_paths
@@ -788,10 +792,10 @@ def apply(
             if device_jpeg == "batch":  # the eligible results in one call, in order; the writer above only marks them
                 together = [i for i, write in enumerate(on_dev) if write is jpeg_device.imwrite_jpeg_tensor]
                 if together:
-                    jpeg_device.imwrite_jpeg_tensors([paths[i] for i in together], [dsts[i] for i in together])
+                    jpeg_device.imwrite_jpeg_tensors([paths[i] for i in together], [dsts[i] for i in together], **jpeg_kw)
             for q, d, write in zip(paths, dsts, on_dev):
                 if write and not (device_jpeg == "batch" and write is jpeg_device.imwrite_jpeg_tensor):
-                    write(q, d)
+                    write(q, d, **(jpeg_kw if device_jpeg and write is jpeg_device.imwrite_jpeg_tensor else {}))
             keep = [i for i, ok in enumerate(on_dev) if not ok]
             paths, results_ = [paths[i] for i in keep], [results[i] for i in keep]
         else:
@@ -1002,6 +1006,7 @@ def apply_lr(
     device_png: bool = False,
     device_jpeg: bool | Literal["batch"] = False,
     device_decode: bool | Literal["batch"] = False,
+    device_jpeg_optimize: bool = False,
 ) -> None:
     """Apply transformer to a pair of images and save them side by side (reference
     remapper.py:406-520).  ``left_path == right_path`` means one file holding both eyes.
@@ -1010,11 +1015,13 @@ def apply_lr(
     (png_device.imwrite_tensor) and the raw result is not copied to the host; ``merge=True`` and other formats take the host route.
     ``device_jpeg=True``: the same for a ``.jpg`` / ``.jpeg`` ``out_path`` of a uint8 result (jpeg_device.imwrite_jpeg_tensor:
     quality 95, 4:2:0, as the host writer).  ``device_jpeg="batch"``: accepted as in ``apply``; the side-by-side frame is a batch of
-    one (jpeg_device.imwrite_jpeg_tensors), the same bytes.
+    one (jpeg_device.imwrite_jpeg_tensors), the same bytes.  ``device_jpeg_optimize=True``: with either mode, the file gets Huffman
+    tables built for the image on the device (``optimize=True`` of jpeg_device.py).
     ``device_decode=True``: ``.jpg`` / ``.jpeg`` inputs are decoded on the device (jpeg_decode_device.py) and only their bytes are
     uploaded; one file holding both eyes is decoded once and the halves are views of it.  Files outside the device decoder's scope
     are read by the host as before.  ``device_decode="batch"``: the same, with the two files decoded as one batch of two."""
     device_jpeg = _device_jpeg_mode(device_jpeg)
+    jpeg_kw = {"optimize": True} if device_jpeg_optimize else {}
     if device_decode:
         if isinstance(left_path, (str, Path)) and isinstance(right_path, (str, Path)) and left_path == right_path:
             both = _decode_on_device([left_path], device, device_decode)[0]
@@ -1062,9 +1069,9 @@ def apply_lr(
 
             if jpeg_device.eligible(out_path, sbs):
                 if device_jpeg == "batch":
-                    jpeg_device.imwrite_jpeg_tensors([out_path], [sbs])
+                    jpeg_device.imwrite_jpeg_tensors([out_path], [sbs], **jpeg_kw)
                 else:
-                    jpeg_device.imwrite_jpeg_tensor(out_path, sbs)
+                    jpeg_device.imwrite_jpeg_tensor(out_path, sbs, **jpeg_kw)
                 LOG.info(f"Saved to {Path(out_path).absolute()}")
                 return
         combine = sbs.cpu().numpy()
