@@ -533,6 +533,42 @@ int v1c_jpeg_decode_batch(int device, void* stream, int n, const uint8_t* const*
                           const int64_t* pitches, const int* out_cns, uint32_t subseq_bits, uint64_t max_workspace_bytes, int* status,
                           v1c_jpeg_decode_report* reports, uint32_t* batch_rounds);
 
+/* ---- progressive JPEG files ("Progressive files"; tests/jpgprog_ref.py restates the contract) ---------------
+ * SOF2 with Huffman coding and 8-bit samples, components and sampling as above, with any legal scan script (ISO/IEC 10918-1 G.1: DC
+ * and AC, first and refinement scans, any band and point transform), DHT, DQT and DRI between the scans.  The two calls above keep
+ * refusing such a file; these two take nothing else (a sequential file is V1C_E_UNSUPPORTED here).  A script that does not bring every
+ * coefficient of every component to full precision is V1C_E_UNSUPPORTED (libjpeg smooths such a file; the contract is the plain
+ * decode), an illegal script V1C_E_CORRUPT, both from the host-only parse.  Every scan is decoded as the sequential decoder's one
+ * scan is -- subsequences, rounds -- into one coefficient store; the pixel stage behind the last scan is the sequential decoder's. */
+typedef struct v1c_jpeg_prog_info_t {
+    int32_t height, width;
+    int32_t components;        /* 1 or 3                                                                                          */
+    int32_t h_samp, v_samp;
+    int32_t scans;
+    uint64_t error_pos;        /* V1C_E_CORRUPT / V1C_E_UNSUPPORTED: byte of the file where the parse stopped                     */
+} v1c_jpeg_prog_info_t;
+
+typedef struct v1c_jpeg_prog_report {
+    uint32_t scans;
+    uint32_t segments;         /* summed over the scans, as the next two                                                          */
+    uint32_t subsequences;
+    uint32_t rounds;
+    uint32_t error_scan;       /* V1C_E_CORRUPT by the decode: the scan (from 0) ...                                              */
+    uint32_t reserved;
+    uint64_t error_pos;        /* ... and the bit of its unstuffed bytes; by the parse: the byte of the file                      */
+} v1c_jpeg_prog_report;
+
+/* Host-only parse of all the scans of a progressive file in HOST memory.  Touches no device.  V1C_E_INVALID for NULL pointers, else
+ * V1C_OK, V1C_E_UNSUPPORTED or V1C_E_CORRUPT.                                                                                    */
+int v1c_jpeg_prog_info(const uint8_t* file, uint64_t size, v1c_jpeg_prog_info_t* info);
+
+/* v1c_jpeg_decode for a progressive file: the same arguments with the same meaning and the same order of checks (arguments and the
+ * parse before any device call, V1C_E_UNSUPPORTED under stream capture, the device's staging buffer and its lock, one stream-ordered
+ * workspace).  The stream is SYNCHRONISED once per round and once for the verdict of EVERY scan.  scan_rounds (may be NULL with
+ * scan_cap 0) receives the rounds of the first scan_cap scans.  The earliest damaged scan's smallest bad bit is reported.         */
+int v1c_jpeg_prog_decode(int device, void* stream, const uint8_t* file, uint64_t size, void* out, int64_t pitch, int out_cn,
+                         uint32_t subseq_bits, v1c_jpeg_prog_report* report, uint32_t* scan_rounds, uint32_t scan_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,7 @@ and destination views (dword-aligned or not), per-unit rotations, apply_lr pairs
 (v1c_remap_lut) on random float32 maps sprinkled with NaN, infinities, 2^15 / 2^26 / 2^31-scale values and ties of the 1/32 grid.
 
     python3 tools/fuzz.py [--seconds 300] [--seed 1] [--big 0.15] [--lut 0.15] [--hot 0.3] [--gen2 0] [--api 0.1] [--auto 0.06] [--fused 0.06] [--log gpurun_out/fuzz.log]
-                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--cases N]
+                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--jpegprog 0] [--cases N]
 
 --wide P: that share of the cases has uint16 or float32 pixels (k_remap_wide): the chain cases above -- same grammar, views, batches, pairs,
 per-unit rotations, graph replays and the same three masks, counted in the same counters -- and the LUT cases (v1c_remap_lut_ex, nothing left
@@ -26,7 +26,9 @@ pipeline of --automatch devfm (features.detect / features.match) against tests/f
 six kinds (noise discs, noise, low contrast, polygons and blobs on a gradient, rendered sphere scenes, flat) of 40 ... 700 px in random views,
 scale, radius, margin, threshold, cell, per_cell and the cap drawn off their defaults, the matcher on the descriptors of two detects or on random
 sets of 0 ... 20000 descriptors with planted copies, duplicates and ties.  A case that v1c_feat_detect refuses (working image under 33 x 33, empty
-circle) where feat_ref.refusal predicts it is correct and not counted (the summary line says how many).  The three shares come off the top of the
+circle) where feat_ref.refusal predicts it is correct and not counted (the summary line says how many).  --jpegprog P: that share goes through the device decoder of progressive JPEG files
+(decode_jpeg_tensor(progressive=True)) -- Pillow's progressive files and tests/jpgprog_cases.py's writer with random legal scan scripts --
+against tests/jpgprog_ref.py: pixels, scans and the rounds of every scan.  These shares come off the top of the
 case draw: with all of them at 0 every earlier seed replays as it ran.
 
 Round 5 added to the grammar: hot shapes of the chains that left the interpreter (planar fisheye -> fisheye, is_latitude_y=False, a
@@ -990,6 +992,80 @@ def jpegdec_case(rng, dev) -> tuple[str, int]:
     return f"JPEGDEC {kind} {(h, w, cn)} seed={seed} quality={quality} sampling={sampling} {how} subseq_bits={S} channels={channels}", bad
 
 
+def jpegprog_case(rng, dev) -> tuple[str, int]:
+    """the device decoder of progressive JPEG files (decode_jpeg_tensor(progressive=True)) against its restatement
+    (jpgprog_ref.decode): the pixels byte for byte, the rounds of every scan and the report.  A random image up to 64 x 64 written
+    progressive by Pillow (its own script, restart options now and then), or its coefficients written again by
+    jpgprog_cases.progressive with a random legal script -- DC interleaved, per component or in groups, random bands, point
+    transforms up to 3 with their refinements in a random order, a restart interval of its own for any scan -- decoded at a random
+    subsequence size"""
+    import jpg_cases as JC
+    import jpgdec_cases as DC
+    import jpgprog_cases as PC
+    import jpgprog_ref as PR
+
+    h, w = (int(v) for v in rng.integers(1, 65, 2))
+    quality = int(rng.choice([10, 50, 75, 90, 95, 100]))
+    kind = str(rng.choice(["smooth", "noise", "flat", "mixed"]))
+    seed = int(rng.integers(0, 1 << 30))
+    cn = 1 if rng.random() < 0.25 else 3
+    if kind == "smooth":
+        img = JC.smooth(h, w, cn, seed)
+    elif kind == "noise":
+        img = JC.noise(h, w, cn, seed)
+    elif kind == "flat":
+        img = np.full((h, w, cn), int(rng.integers(0, 256)), np.uint8)
+    else:
+        img = np.where(JC.noise(h, w, 1, seed) > 200, JC.noise(h, w, cn, seed + 1), JC.smooth(h, w, cn, seed + 2))
+    img = np.ascontiguousarray(img)
+    sampling = str(rng.choice(["444", "422", "420"]))
+    if rng.random() < 0.35:
+        kw = {}
+        r = rng.random()
+        if r < 0.25:
+            kw["restart_marker_blocks"] = int(rng.integers(1, 12))
+        elif r < 0.4:
+            kw["restart_marker_rows"] = int(rng.integers(1, 4))
+        data = DC.pillow(img, quality, sampling, progressive=True, **kw)
+        how = f"Pillow {kw!r}"
+    else:
+        comps = list(range(cn))
+        groups = [comps] if rng.random() < 0.5 else [[c] for c in comps] if rng.random() < 0.6 or cn == 1 else [[0], [1, 2]]
+        chains = []
+        for g in groups:                                   # DC: first scan and refinements of every group
+            al = int(rng.integers(0, 3))
+            chains.append([PC.scan(g, 0, 0, 0, al)] + [PC.scan(g, 0, 0, a, a - 1) for a in range(al, 0, -1)])
+        dc = [sc for ch in chains for sc in ch[:1]]
+        chains = [ch[1:] for ch in chains if len(ch) > 1]
+        for c in comps:                                    # AC: random bands, each a chain of its own
+            cuts = sorted(set(int(v) for v in rng.integers(2, 64, int(rng.integers(0, 4)))))
+            for a, e in zip([1] + cuts, [v - 1 for v in cuts] + [63]):
+                al = int(rng.integers(0, 4)) if rng.random() < 0.6 else 0
+                chains.append([PC.scan([c], a, e, 0, al)] + [PC.scan([c], a, e, k, k - 1) for k in range(al, 0, -1)])
+        script = dc
+        while chains:                                      # the chains interleaved at random, each in its own order
+            i = int(rng.integers(0, len(chains)))
+            script.append(chains[i].pop(0))
+            if not chains[i]:
+                chains.pop(i)
+        for sc in script:
+            if rng.random() < 0.25:
+                sc["dri"] = int(rng.choice([0, 1, 2, 3, 7, 65535]))
+        data = PC.from_sequential(DC.pillow(img, quality, sampling), script)
+        how = f"writer scans={len(script)} " + " ".join(f"{''.join(map(str, sc['comps']))}:{sc['Ss']}-{sc['Se']}:{sc['Ah']}{sc['Al']}" +
+                                                           (f":dri{sc['dri']}" if sc["dri"] is not None else "") for sc in script)
+    S = int(rng.choice([0, 256, 256, 288, 512, 1024]))
+    channels = 1 if cn == 1 and rng.random() < 0.5 else 3
+    got = V.decode_jpeg_tensor(data, channels=channels, subseq_bits=S or None, progressive=True).cpu().numpy()
+    rep = V.last_decode_report()
+    want = PR.decode(data, S, channels=channels, check=False)
+    KINDS["jpegprog"] = KINDS.get("jpegprog", 0) + 1
+    bad = int((got != want.pixels).sum()) if got.shape == want.pixels.shape else got.size
+    bad += 0 if (rep["scans"], rep["segments"], rep["subsequences"], rep["scan_rounds"]) == (want.scans, want.segments, want.subsequences,
+                                                                                             want.scan_rounds) else 1
+    return f"JPEGPROG {kind} {(h, w, cn)} seed={seed} quality={quality} sampling={sampling} {how} subseq_bits={S} channels={channels}", bad
+
+
 FEAT = {"drawn": 0, "refused": 0}  # feat cases drawn / of them refused by v1c_feat_detect as feat_ref.refusal predicts (not counted)
 FEAT_IMAGES = ["disc", "noise", "low", "scene", "sphere", "flat"]
 FEAT_RATIOS = [(3, 4), (1, 1), (1, 2), (0, 1)]
@@ -1156,6 +1232,7 @@ def main() -> int:
     ap.add_argument("--jpegdec", type=float, default=0.0, help="share of cases through the device JPEG decoder (decode_jpeg_tensor) against jpgdec_ref.decode")
     ap.add_argument("--jpegbatch", type=float, default=0.0, help="share of cases through the batched device JPEG encoder (encode_jpeg_tensors) against the single calls and jpg_ref.encode")
     ap.add_argument("--jpegopt", type=float, default=0.0, help="share of cases through the device JPEG encoder with optimised Huffman tables (optimize=True, single and batched) against jpg_opt_ref.encode")
+    ap.add_argument("--jpegprog", type=float, default=0.0, help="share of cases through the device decoder of progressive JPEG files (decode_jpeg_tensor(progressive=True)) against jpgprog_ref.decode")
     ap.add_argument("--cases", type=int, default=None, help="stop after this many cases (before --seconds runs out)")
     ap.add_argument("--feat", type=float, default=0.0, help="share of cases through the feature pipeline (features.detect / features.match) against tests/feat_ref.py")
     ap.add_argument("--only", type=int, default=None, help="run only this case number (reproduce)")
@@ -1190,10 +1267,12 @@ def main() -> int:
             r_kind = rng.random()
             wide_chain = False
             counted = True
-            top = 1.0 - a.jpegopt - a.jpegbatch - a.jpegdec
-            if r_kind >= 1.0 - a.jpegopt:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+            top = 1.0 - a.jpegprog - a.jpegopt - a.jpegbatch - a.jpegdec
+            if r_kind >= 1.0 - a.jpegprog:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+                desc, bad = jpegprog_case(rng, dev)
+            elif r_kind >= 1.0 - a.jpegprog - a.jpegopt:
                 desc, bad = jpegopt_case(rng, dev)
-            elif r_kind >= 1.0 - a.jpegopt - a.jpegbatch:
+            elif r_kind >= 1.0 - a.jpegprog - a.jpegopt - a.jpegbatch:
                 desc, bad = jpegbatch_case(rng, dev)
             elif r_kind >= top:
                 desc, bad = jpegdec_case(rng, dev)

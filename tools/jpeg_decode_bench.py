@@ -11,6 +11,10 @@ JSON line per (file, subseq_bits); ``--out`` appends them to a file.
 ``decode_jpeg_tensor`` calls in the same process, the two alternating run by run; one JSON line per (file, N) with the times, the
 rounds of both and whether the tensors are equal.
 
+``--progressive``: every file is first written again as a progressive file by Pillow (the same quantisation tables and sampling:
+``quality="keep"``), and decoded with ``progressive=True``; the JSON line has the scans and the rounds of every scan too.
+
+    python tools/jpeg_decode_bench.py --progressive --out profiles/jpeg_decode_progressive/bench.jsonl
     python tools/jpeg_decode_bench.py --subseq-bits 512 1024 2048 4096 --out profiles/jpeg_decode/bench.jsonl
     python tools/jpeg_decode_bench.py --batch 2 16 64 --out profiles/jpeg_decode_batch/bench.jsonl
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/jpeg_decode_bench.py --runs 2 --device-only     (per-kernel times)
@@ -110,6 +114,7 @@ def main() -> None:
     ap.add_argument("--device-only", action="store_true", help="skip the host path (profiler runs)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--batch", type=int, nargs="+", default=None, help="batch sizes: N copies in one decode_jpeg_tensors call against N single calls")
+    ap.add_argument("--progressive", action="store_true", help="the files written again progressive by Pillow, decoded with progressive=True")
     ap.add_argument("--only", nargs="*", default=[], help="with --batch: only these file:N pairs (docs_2048:64 ...)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -120,6 +125,15 @@ def main() -> None:
 
     dev = torch.device("cuda", 0)
     files = {Path(f).name: Path(f).read_bytes() for f in a.files} if a.files else default_files()
+    dkw = {}
+    if a.progressive:
+        if a.batch:
+            raise SystemExit("--progressive has no batch: decode_jpeg_tensors refuses progressive files")
+        for name in list(files):
+            b = io.BytesIO()
+            Image.open(io.BytesIO(files.pop(name))).save(b, "JPEG", quality="keep", subsampling="keep", progressive=True)
+            files[name + "_progressive"] = b.getvalue()
+        dkw = {"progressive": True}
     if a.batch:
         bench_batches(V, files, a.batch, a.subseq_bits, a.runs, set(a.only), a.out)
         return
@@ -142,11 +156,11 @@ def main() -> None:
         parse = []
         for _ in range(max(a.runs, 3)):
             t0 = time.perf_counter()
-            J.probe(data)
+            (J.probe_progressive if a.progressive else J.probe)(data)
             parse.append(1e3 * (time.perf_counter() - t0))
         parse.sort()
         for S in a.subseq_bits:
-            kw = {} if S == 0 else {"subseq_bits": S}
+            kw = {**dkw} if S == 0 else {"subseq_bits": S, **dkw}
             out = V.decode_jpeg_tensor(data, **kw)  # warm-up: code objects, the staging buffer, the memory pool
             torch.cuda.synchronize()
             rep = V.last_decode_report()

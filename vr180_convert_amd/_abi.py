@@ -61,6 +61,16 @@ class Unit(C.Structure):
     ]
 
 
+class JpegProgInfo(C.Structure):
+    """v1c_jpeg_prog_info_t"""
+    _fields_ = [(n, C.c_int32) for n in ("height", "width", "components", "h_samp", "v_samp", "scans")] + [("error_pos", C.c_uint64)]
+
+
+class JpegProgReport(C.Structure):
+    """v1c_jpeg_prog_report"""
+    _fields_ = [(n, C.c_uint32) for n in ("scans", "segments", "subsequences", "rounds", "error_scan", "reserved")] + [("error_pos", C.c_uint64)]
+
+
 def op(opcode: int, iparam: int = 0, params: Sequence[float] = ()) -> Op:
     params = list(params)
     if len(params) > MAX_PARAMS:

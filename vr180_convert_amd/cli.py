@@ -225,6 +225,9 @@ def lr(
     device_jpeg_optimize: Annotated[bool, typer.Option("--device-jpeg-optimize", help="With --device-jpeg or --device-jpeg-batch: Huffman "
                                                                                        "tables built for each image on the GPU (smaller "
                                                                                        "files, the same pixels)")] = False,
+    device_decode_progressive: Annotated[bool, typer.Option("--device-decode-progressive", help="With --device-decode or --device-decode-batch: "
+                                                                                                 "progressive JPEG inputs are decoded on "
+                                                                                                 "the GPU too")] = False,
 ) -> None:
     """Remap a pair of fisheye images to a pair of SBS equirectangular images."""
     from .remapper import apply_lr
@@ -252,7 +255,8 @@ def lr(
         # decoded once, here: the matcher and apply_lr both take the tensors (apply_lr passes what is no path through)
         from . import jpeg_decode_device
 
-        left_in, right_in = jpeg_decode_device.read_inputs([left_path, right_path], **({"batch": True} if device_decode_batch else {}))
+        left_in, right_in = jpeg_decode_device.read_inputs([left_path, right_path], **({"batch": True} if device_decode_batch else {}),
+                                                                **({"progressive": True} if device_decode_progressive else {}))
     if automatch != "":
         match_image = out.with_suffix(f".match{out.suffix}") if savematch else None  # cli.py:362-365
         chain = calibrated_pair(chain, automatch, left_in, right_in, radius_, match_image)
@@ -261,7 +265,8 @@ def lr(
              interpolation=interp, boarder_mode=border, boarder_value=border_value, merge=merge,
              **({"device_png": True} if device_png else {}), **({"device_jpeg": "batch"} if device_jpeg_batch else {"device_jpeg": True} if device_jpeg else {}),
              **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}),
-             **({"device_jpeg_optimize": True} if device_jpeg_optimize else {}))
+             **({"device_jpeg_optimize": True} if device_jpeg_optimize else {}),
+             **({"device_decode_progressive": True} if device_decode_progressive else {}))
 
 
 @app.command()
@@ -287,6 +292,9 @@ def s(
     device_jpeg_optimize: Annotated[bool, typer.Option("--device-jpeg-optimize", help="With --device-jpeg or --device-jpeg-batch: Huffman "
                                                                                        "tables built for each image on the GPU (smaller "
                                                                                        "files, the same pixels)")] = False,
+    device_decode_progressive: Annotated[bool, typer.Option("--device-decode-progressive", help="With --device-decode or --device-decode-batch: "
+                                                                                                 "progressive JPEG inputs are decoded on "
+                                                                                                 "the GPU too")] = False,
 ) -> None:
     """Remap fisheye images to equirectangular images (one shared map for all of them)."""
     from .remapper import apply
@@ -304,7 +312,8 @@ def s(
           boarder_mode=_flag(boarder_mode, _BORDERS, "border_", "border mode"), boarder_value=boarder_value,
           **({"device_png": True} if device_png else {}), **({"device_jpeg": "batch"} if device_jpeg_batch else {"device_jpeg": True} if device_jpeg else {}),
           **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}),
-          **({"device_jpeg_optimize": True} if device_jpeg_optimize else {}))
+          **({"device_jpeg_optimize": True} if device_jpeg_optimize else {}),
+          **({"device_decode_progressive": True} if device_decode_progressive else {}))
 
 
 @app.command()

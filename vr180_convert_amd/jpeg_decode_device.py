@@ -7,6 +7,12 @@ Baseline and extended sequential Huffman files (SOF0 / SOF1, 8-bit) of one compo
 tables and any restart interval or none; the pixels are libjpeg's default decode (INTEGRATION.md section 8 has the contract,
 ``tests/jpgdec_ref.py`` restates it).  Anything else raises ``NotImplementedError`` from a host-only parse, a damaged file
 ``ValueError``: nothing falls back silently.
+
+``progressive=True`` adds progressive Huffman files (SOF2) of the same components and samplings with any legal scan script that
+brings every coefficient to full precision: every scan is decoded as the one scan of a sequential file is, into one coefficient store
+(``v1c_jpeg_prog_decode``, csrc/kernels_jpegprog.hip; ``tests/jpgprog_ref.py`` restates the contract).  Off by default: AC refinement
+scans take about one round per subsequence, so large files without restart markers decode far slower than on the host (DESIGN.md
+section 18).
 """
 from __future__ import annotations
 
@@ -60,19 +66,54 @@ def probe(data_or_path: Any) -> tuple[int, int, int]:
     return info.height, info.width, info.components
 
 
-def decode_jpeg_tensor(data_or_path: Any, *, device: Any = None, channels: int = 3, subseq_bits: int | None = None) -> torch.Tensor:
+def probe_progressive(data_or_path: Any) -> tuple[int, int, int, int]:
+    """(height, width, components, scans) of a PROGRESSIVE file the device decodes (``decode_jpeg_tensor(..., progressive=True)``), by
+    the host-only parse of all its scans; ``NotImplementedError`` -- for a sequential file too -- / ``CorruptJPEG`` otherwise"""
+    data = _bytes_of(data_or_path)
+    info = _abi.JpegProgInfo()
+    _check(_native.lib().v1c_jpeg_prog_info(data, len(data), C.byref(info)), "v1c_jpeg_prog_info")
+    return info.height, info.width, info.components, info.scans
+
+
+def _decode_progressive(data: bytes, device: Any, channels: int, S: int) -> torch.Tensor:
+    h, w, nc, scans = probe_progressive(data)
+    if channels == 1 and nc != 1:
+        raise ValueError("channels=1 takes a grey file")
+    dev = _device(device)
+    out = torch.empty((h, w) if channels == 1 else (h, w, 3), dtype=torch.uint8, device=dev)
+    rep = _abi.JpegProgReport()
+    per_scan = (C.c_uint32 * scans)()
+    rc = _native.lib().v1c_jpeg_prog_decode(dev.index, _stream_ptr(dev), data, len(data), out.data_ptr(), w * channels, channels, S,
+                                            C.byref(rep), per_scan, scans)
+    _check(rc, "v1c_jpeg_prog_decode")
+    _last.clear()
+    _last.update(segments=rep.segments, subsequences=rep.subsequences, rounds=rep.rounds, path="device", scans=rep.scans,
+                 scan_rounds=list(per_scan))
+    return out
+
+
+def decode_jpeg_tensor(data_or_path: Any, *, device: Any = None, channels: int = 3, subseq_bits: int | None = None,
+                       progressive: bool = False) -> torch.Tensor:
     """A JPEG file (its bytes, or a path) as a CUDA ``uint8`` tensor in cv2 channel order, decoded on the device on the current
     stream: ``(H, W, 3)`` BGR (a grey file replicated, as ``cv2.imread`` does), or ``(H, W)`` with ``channels=1`` for a grey file.
     ``subseq_bits``: bits of the scan one lane decodes, a multiple of 32 from 256 (None: the engine's default); the pixels do not
     depend on it.  EXIF orientation is not applied.  Raises ``NotImplementedError`` for a file outside the device decoder's scope and
-    ``CorruptJPEG`` (a ``ValueError``) for a damaged one; ``last_decode_report()`` tells what the call did."""
+    ``CorruptJPEG`` (a ``ValueError``) for a damaged one; ``last_decode_report()`` tells what the call did.
+    ``progressive=True``: a progressive Huffman file (SOF2) of the same components and samplings, with any legal scan script that
+    brings every coefficient to full precision, is decoded on the device too, scan by scan (``v1c_jpeg_prog_decode``); sequential
+    files are decoded exactly as without it.  Off, such a file is refused as ever."""
     if channels not in (1, 3):
         raise ValueError("channels must be 1 or 3")
     S = 0 if subseq_bits is None else int(subseq_bits)
     if S and (S % 32 or S < 256):
         raise ValueError("subseq_bits must be a multiple of 32, at least 256")
     data = _bytes_of(data_or_path)
-    h, w, nc = probe(data)
+    try:
+        h, w, nc = probe(data)
+    except NotImplementedError:
+        if not progressive or not _is_progressive(data):
+            raise
+        return _decode_progressive(data, device, channels, S)
     if channels == 1 and nc != 1:
         raise ValueError("channels=1 takes a grey file")
     dev = _device(device)
@@ -85,14 +126,34 @@ def decode_jpeg_tensor(data_or_path: Any, *, device: Any = None, channels: int =
     return out
 
 
-def imread_tensor(path: Any, *, device: Any = None, channels: int = 3, subseq_bits: int | None = None) -> torch.Tensor:
+def _is_progressive(data: bytes) -> bool:
+    """whether the host-only parse of the progressive decoder is the one to ask: the file's frame header is SOF2"""
+    pos = 2
+    while pos + 4 <= len(data) and data[pos] == 0xFF:
+        m = data[pos + 1]
+        if m == 0xFF:
+            pos += 1
+        elif m == 0x01 or 0xD0 <= m <= 0xD8:
+            pos += 2
+        elif 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            return m == 0xC2
+        elif m in (0xD9, 0xDA):
+            return False
+        else:
+            pos += 2 + (data[pos + 2] << 8 | data[pos + 3])
+    return False
+
+
+def imread_tensor(path: Any, *, device: Any = None, channels: int = 3, subseq_bits: int | None = None,
+                  progressive: bool = False) -> torch.Tensor:
     """``decode_jpeg_tensor`` of a file"""
-    return decode_jpeg_tensor(Path(path), device=device, channels=channels, subseq_bits=subseq_bits)
+    return decode_jpeg_tensor(Path(path), device=device, channels=channels, subseq_bits=subseq_bits, progressive=progressive)
 
 
 def last_decode_report() -> dict:
     """of the last successful decode: ``segments`` (stretches between restart markers), ``subsequences`` (lanes), ``rounds`` (launches
-    until the entry states stood still) and ``path="device"``"""
+    until the entry states stood still) and ``path="device"``; after a progressive file the three are summed over its scans, and
+    ``scans`` and ``scan_rounds`` (a list) are there too"""
     return dict(_last)
 
 
@@ -187,17 +248,24 @@ def last_batch_report() -> dict:
     return dict(_last_batch)
 
 
-def read_inputs(items: Any, *, device: Any = None, batch: bool = False) -> list:
+def read_inputs(items: Any, *, device: Any = None, batch: bool = False, progressive: bool = False) -> list:
     """What ``device_decode=True`` does with its inputs: the ``.jpg`` / ``.jpeg`` paths among ``items`` become BGR device tensors; every
     other entry (arrays, tensors, other suffixes) is handed back as it is.  A file outside the device decoder's scope (progressive,
     ...) stays a path for the host reader; so does one that is damaged or cannot be read, with a warning, so that such a file meets
     the host reader's behaviour as it does without the option.  Any other error is raised.  ``batch=True`` (``device_decode="batch"``):
-    the same outcomes and log lines from one ``imread_tensors`` call over all the eligible paths."""
+    the same outcomes and log lines from one ``imread_tensors`` call over all the eligible paths.  ``progressive=True``
+    (``device_decode_progressive``): a progressive file stays on the device too -- under ``batch`` by a single call of its own behind
+    the batch, which keeps refusing it."""
     if batch:
         items = list(items)
         at = [i for i, q in enumerate(items) if eligible(q)]
         got = imread_tensors([items[i] for i in at], device=device, errors="return") if at else []
         for i, t in zip(at, got):
+            if isinstance(t, NotImplementedError) and progressive:
+                try:
+                    t = imread_tensor(items[i], device=device, progressive=True)
+                except (NotImplementedError, CorruptJPEG, OSError) as e:
+                    t = e
             if isinstance(t, NotImplementedError):
                 LOG.info(f"{items[i]}: read on the host ({t})")
             elif isinstance(t, (CorruptJPEG, OSError)):
@@ -211,7 +279,7 @@ def read_inputs(items: Any, *, device: Any = None, batch: bool = False) -> list:
     for q in items:
         if eligible(q):
             try:
-                q = imread_tensor(q, device=device)
+                q = imread_tensor(q, device=device, progressive=progressive)
             except NotImplementedError as e:
                 LOG.info(f"{q}: read on the host ({e})")
             except (CorruptJPEG, OSError) as e:
@@ -226,4 +294,4 @@ def eligible(path: Any) -> bool:
 
 
 __all__ = ["decode_jpeg_tensor", "imread_tensor", "decode_jpeg_tensors", "imread_tensors", "read_inputs", "last_decode_report",
-           "last_batch_report", "eligible", "probe", "CorruptJPEG"]
+           "last_batch_report", "eligible", "probe", "probe_progressive", "CorruptJPEG"]

@@ -675,16 +675,18 @@ def _to_device(img: Any, dev: torch.device) -> torch.Tensor:
     return torch.from_numpy(a).to(dev, non_blocking=False)
 
 
-def _decode_on_device(items: Sequence[Any], device: Any, mode: Any = True) -> list:
+def _decode_on_device(items: Sequence[Any], device: Any, mode: Any = True, progressive: bool = False) -> list:
     """``device_decode=True``: jpeg_decode_device.read_inputs -- ``.jpg`` / ``.jpeg`` paths decoded on the device, everything else and
-    files the device decoder does not take left for ``_io.imread``; ``device_decode="batch"``: the same through one batched decode"""
+    files the device decoder does not take left for ``_io.imread``; ``device_decode="batch"``: the same through one batched decode;
+    ``progressive`` (``device_decode_progressive``): progressive files stay on the device too"""
     from . import jpeg_decode_device
 
     if isinstance(mode, str) and mode != "batch":
         raise ValueError('device_decode must be True, False or "batch"')
+    kw: dict = {"progressive": True} if progressive else {}
     if mode == "batch":
-        return jpeg_decode_device.read_inputs(items, device=device, batch=True)
-    return jpeg_decode_device.read_inputs(items, device=device)
+        return jpeg_decode_device.read_inputs(items, device=device, batch=True, **kw)
+    return jpeg_decode_device.read_inputs(items, device=device, **kw)
 
 
 def _device_jpeg_mode(mode: Any) -> Any:
@@ -709,6 +711,7 @@ def apply(
     device_jpeg: bool | Literal["batch"] = False,
     device_decode: bool | Literal["batch"] = False,
     device_jpeg_optimize: bool = False,
+    device_decode_progressive: bool = False,
 ) -> Sequence[NDArray[np.uint8]]:
     """Apply transformer to images (reference remapper.py:324-403).
 
@@ -727,7 +730,9 @@ def apply(
     and its two synchronisations (jpeg_device.imwrite_jpeg_tensors); the files are the same bytes.  The other results take the paths
     they take without it (``device_png``, the host writer).  ``device_jpeg_optimize=True``: those files get Huffman tables built for
     each image on the device (``optimize=True`` of jpeg_device.py: smaller files, the same pixels) with either ``device_jpeg`` mode;
-    it does nothing without one."""
+    it does nothing without one.  ``device_decode_progressive=True``: with either ``device_decode`` mode, progressive JPEG inputs are
+    decoded on the device too (``progressive=True`` of jpeg_decode_device.py; under ``"batch"`` each by a call of its own behind the
+    batch) instead of going to the host reader; it does nothing without ``device_decode``."""
     device_jpeg = _device_jpeg_mode(device_jpeg)
     jpeg_kw = {"optimize": True} if device_jpeg_optimize else {}
     in_paths_ = [in_paths] if isinstance(in_paths, (str, Path, np.ndarray, torch.Tensor)) else in_paths
@@ -735,7 +740,7 @@ def apply(
     del in_paths, out_paths
 
     if device_decode:
-        in_paths_ = _decode_on_device(list(in_paths_), device, device_decode)
+        in_paths_ = _decode_on_device(list(in_paths_), device, device_decode, device_decode_progressive)
     images = _io.imread_many(list(in_paths_))
     if device_decode:
         decoded = next((im for im in images if isinstance(im, torch.Tensor) and im.is_cuda), None)
@@ -1007,6 +1012,7 @@ def apply_lr(
     device_jpeg: bool | Literal["batch"] = False,
     device_decode: bool | Literal["batch"] = False,
     device_jpeg_optimize: bool = False,
+    device_decode_progressive: bool = False,
 ) -> None:
     """Apply transformer to a pair of images and save them side by side (reference
     remapper.py:406-520).  ``left_path == right_path`` means one file holding both eyes.
@@ -1019,16 +1025,18 @@ def apply_lr(
     tables built for the image on the device (``optimize=True`` of jpeg_device.py).
     ``device_decode=True``: ``.jpg`` / ``.jpeg`` inputs are decoded on the device (jpeg_decode_device.py) and only their bytes are
     uploaded; one file holding both eyes is decoded once and the halves are views of it.  Files outside the device decoder's scope
-    are read by the host as before.  ``device_decode="batch"``: the same, with the two files decoded as one batch of two."""
+    are read by the host as before.  ``device_decode="batch"``: the same, with the two files decoded as one batch of two.
+    ``device_decode_progressive=True``: with either mode, progressive JPEG inputs are decoded on the device too instead of going to the
+    host reader (``progressive=True`` of jpeg_decode_device.py)."""
     device_jpeg = _device_jpeg_mode(device_jpeg)
     jpeg_kw = {"optimize": True} if device_jpeg_optimize else {}
     if device_decode:
         if isinstance(left_path, (str, Path)) and isinstance(right_path, (str, Path)) and left_path == right_path:
-            both = _decode_on_device([left_path], device, device_decode)[0]
+            both = _decode_on_device([left_path], device, device_decode, device_decode_progressive)[0]
             if isinstance(both, torch.Tensor):
                 left_path, right_path = both[:, : both.shape[1] // 2], both[:, both.shape[1] // 2 :]
         else:
-            left_path, right_path = _decode_on_device([left_path, right_path], device, device_decode)
+            left_path, right_path = _decode_on_device([left_path, right_path], device, device_decode, device_decode_progressive)
     if isinstance(left_path, (str, Path)) and isinstance(right_path, (str, Path)) and left_path == right_path:
         image = _io.imread(left_path)
         left_path = image[:, : image.shape[1] // 2]
