@@ -569,6 +569,68 @@ int v1c_jpeg_prog_info(const uint8_t* file, uint64_t size, v1c_jpeg_prog_info_t*
 int v1c_jpeg_prog_decode(int device, void* stream, const uint8_t* file, uint64_t size, void* out, int64_t pitch, int out_cn,
                          uint32_t subseq_bits, v1c_jpeg_prog_report* report, uint32_t* scan_rounds, uint32_t scan_cap);
 
+/* ---- lossless JPEG crop, split and swap (INTEGRATION.md section 9 states the contract; tests/jpgxc_ref.py restates it) ----------------
+ * A file that v1c_jpeg_decode_info accepts -- one component, or three in 4:4:4, 4:2:2 or 4:2:0 -- is cut on MCU boundaries in the DCT domain:
+ * the entropy decoder of v1c_jpeg_decode runs up to its DC scan, a gather kernel copies rectangles of MCUs into the encoder's
+ * coefficient store, and the stages of v1c_jpeg_encode behind its transform code them again.  No coefficient changes, so every sample
+ * a reader decodes from the gathered MCUs is the sample it decodes from the source; only the Huffman coding and the restart intervals
+ * are the outputs' own.  An output is tiled by regions: a rectangle of nx x ny source MCUs from MCU (src_x, src_y), placed with its
+ * first MCU at MCU (dst_x, dst_y) of the output.  An MCU is 8 x 8 pixels (one component, 4:4:4), 16 x 8 (4:2:2) or 16 x 16 (4:2:0).  A crop is one
+ * output of one region, a split two outputs of one region each, a swap of the halves one output of two regions.  A region may hold the
+ * source's partial last MCU column or row.  An output's width and height are the caller's: its MCU columns and rows are those of that
+ * size, and the regions must cover each of them exactly once.
+ * V1C_E_UNSUPPORTED from the host-only parse for what v1c_jpeg_decode_info refuses (progressive files among it), for
+ * Cb and Cr with different quantisation tables, and for regions that overlap in an output; V1C_E_CORRUPT for a damaged file;
+ * V1C_E_INVALID for every other rule of the regions (outside the source or the output, an MCU of the output uncovered, more than
+ * V1C_JPEG_XC_MAX_REGIONS of them), sizes, restart_mcus outside 0 ... 65535, capacity.  All before any device call.                    */
+#define V1C_JPEG_XC_MAX_REGIONS 16
+#define V1C_JPEG_XC_MAX_OUTPUTS 16
+#define V1C_JPEG_HEADER_XC_MAX 2048           /* bytes v1c_jpeg_header_xc can write                                                 */
+
+typedef struct v1c_jpeg_xc_region {   /* in MCUs                                                                                  */
+    int32_t src_x, src_y, nx, ny, dst_x, dst_y;
+} v1c_jpeg_xc_region;
+
+typedef struct v1c_jpeg_xc_output {
+    int32_t width, height;            /* pixels                                                                                  */
+    int32_t restart_mcus;             /* MCUs per restart interval, 1 ... 65535; 0: no restart markers and no DRI                */
+    int32_t optimize;                 /* != 0: Huffman tables of its own, as v1c_jpeg_encode_opt builds them                     */
+    int32_t nregions, reserved;
+    const v1c_jpeg_xc_region* regions;
+    uint8_t* out_host;                /* HOST memory for the scan, page-locked recommended                                       */
+    uint64_t capacity;                /* >= v1c_jpeg_transcode_bound of this output                                              */
+    uint64_t size;                    /* out: bytes of its scan                                                                  */
+    uint32_t dht_size;                /* out: bytes of dht, 0 for optimize == 0                                                  */
+    uint8_t dht[V1C_JPEG_DHT_MAX];    /* out: the DHT segment's body                                                             */
+} v1c_jpeg_xc_output;
+
+/* Bytes the scan of a width x height output of the file can need (v1c_jpeg_bound's rule for the file's components and sampling).
+ * Host-only.  0 for a file the transcoder refuses or sizes out of range.                                                          */
+uint64_t v1c_jpeg_transcode_bound(const uint8_t* file, uint64_t size, int width, int height, int restart_mcus);
+
+/* Every check of v1c_jpeg_transcode that needs no device, and nothing else: the parse, the file's scope, every output's rules
+ * (out_host and capacity are not looked at).  Touches no device.  *error_pos (may be NULL): where a parse stopped.               */
+int v1c_jpeg_transcode_check(const uint8_t* file, uint64_t size, int n, const v1c_jpeg_xc_output* outputs, uint64_t* error_pos);
+
+/* Everything of an output's file in front of its scan into the HOST buffer `out`: SOI, APP0 (JFIF), DQT with the FILE's tables, SOF0
+ * (SOF1 where a table has 16-bit entries) with the output's size and the file's sampling factors, DHT (dht of dht_size bytes as
+ * v1c_jpeg_transcode returned it, or NULL for the Annex K tables), DRI unless restart_mcus is 0, SOS.  The source's APPn and COM
+ * segments are not carried over.  The output's file is these bytes, its scan and EOI.  Host-only.  Returns the number of bytes, or
+ * the parse's code, or V1C_E_INVALID.                                                                                              */
+int64_t v1c_jpeg_header_xc(const uint8_t* file, uint64_t size, int width, int height, int restart_mcus, const uint8_t* dht,
+                           uint32_t dht_size, uint8_t* out, uint64_t capacity);
+
+/* Transcodes the file (HOST memory) into n outputs on `stream`: every out_host receives the scan of its output, `size` its size and,
+ * for an optimising output, dht / dht_size its tables.  The scan is byte for byte what the encoder writes for the gathered
+ * coefficients with those tables and that restart interval.  subseq_bits and report as v1c_jpeg_decode.  The call SYNCHRONISES the
+ * stream once per round of the decode, once for the verdict on the stream and on the coefficients' range, and twice for the sizes
+ * and the scans, as v1c_jpeg_encode_batch does.  V1C_E_UNSUPPORTED, before anything is done on the device, while `stream` is being
+ * captured into a graph; V1C_E_CORRUPT where the last pass of the decode finds the entropy-coded data damaged (report->error_pos: the
+ * bit); V1C_E_UNSUPPORTED where a coefficient of a GATHERED block is outside what 8-bit samples give (an AC coefficient beyond
+ * +-1023, a DC outside -1024 ... 1023, judged before it is cut to 16 bits): the encoder's tables do not code it.  After an error the outputs' content is unspecified.                       */
+int v1c_jpeg_transcode(int device, void* stream, const uint8_t* file, uint64_t size, int n, v1c_jpeg_xc_output* outputs,
+                       uint32_t subseq_bits, v1c_jpeg_decode_report* report);
+
 #ifdef __cplusplus
 }
 #endif

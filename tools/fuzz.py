@@ -7,7 +7,7 @@ and destination views (dword-aligned or not), per-unit rotations, apply_lr pairs
 (v1c_remap_lut) on random float32 maps sprinkled with NaN, infinities, 2^15 / 2^26 / 2^31-scale values and ties of the 1/32 grid.
 
     python3 tools/fuzz.py [--seconds 300] [--seed 1] [--big 0.15] [--lut 0.15] [--hot 0.3] [--gen2 0] [--api 0.1] [--auto 0.06] [--fused 0.06] [--log gpurun_out/fuzz.log]
-                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--jpegprog 0] [--cases N]
+                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--jpegprog 0] [--jpegxc 0] [--cases N]
 
 --wide P: that share of the cases has uint16 or float32 pixels (k_remap_wide): the chain cases above -- same grammar, views, batches, pairs,
 per-unit rotations, graph replays and the same three masks, counted in the same counters -- and the LUT cases (v1c_remap_lut_ex, nothing left
@@ -938,6 +938,87 @@ def jpegopt_case(rng, dev) -> tuple[str, int]:
             f"restart_mcus={restarts!r} {' '.join(kinds)}"), bad
 
 
+def jpegxc_case(rng, dev) -> tuple[str, int]:
+    """the lossless JPEG transcoder (jpeg_transcode_device.transcode_regions) against its restatement (jpgxc_ref.transcode), the files
+    byte for byte: a random image up to 160 x 160 -- smooth, noise, flat, mixed -- written by Pillow (grey, 4:4:4, 4:2:2 or 4:2:0, any quality,
+    optimised tables now and then) or by the encoder's restatement (any restart interval), cut into one to three outputs of one to four
+    random regions each -- crops, splits, swaps, shuffled strips --, each with its own restart interval (a row, none, any) and tables;
+    now and then a list the contract refuses (overlapping or missing regions), which must be refused the restatement's way"""
+    import jpg_cases as JC
+    import jpg_ref as JR
+    import jpgdec_cases as DC
+    import jpgxc_ref as XR
+    from vr180_convert_amd import jpeg_transcode_device as T
+
+    h, w = (int(v) for v in rng.integers(1, 161, 2))
+    quality = int(rng.choice([1, 10, 50, 75, 90, 95, 100])) if rng.random() < 0.7 else int(rng.integers(1, 101))
+    kind = str(rng.choice(["smooth", "noise", "flat", "mixed"]))
+    seed = int(rng.integers(0, 1 << 30))
+    cn = 1 if rng.random() < 0.2 else 3
+    if kind == "smooth":
+        img = JC.smooth(h, w, cn, seed)
+    elif kind == "noise":
+        img = JC.noise(h, w, cn, seed)
+    elif kind == "flat":
+        img = np.full((h, w, cn), int(rng.integers(0, 256)), np.uint8)
+    else:
+        img = np.where(JC.noise(h, w, 1, seed) > 200, JC.noise(h, w, cn, seed + 1), JC.smooth(h, w, cn, seed + 2))
+    img = np.ascontiguousarray(img)
+    refuse = rng.random() < 0.08
+    sampling = str(rng.choice(["420", "420", "444", "422"]))
+    if sampling != "422" and rng.random() < 0.4:
+        m = 16 if (cn != 1 and sampling == "420") else 8
+        nmcu = -(-h // m) * -(-w // m)
+        restart = 1 if rng.random() < 0.2 else int(rng.integers(1, nmcu + 2))
+        data = JR.encode(img, quality, sampling, restart)
+        how = f"jpg_ref restart_mcus={restart}"
+    else:
+        kw = {"optimize": True} if rng.random() < 0.3 else {}
+        data = DC.pillow(img, quality, sampling, **kw)
+        how = f"Pillow {kw!r}"
+    mw = 8 if cn == 1 else {"444": 8, "422": 16, "420": 16}[sampling]
+    mh = 16 if (cn == 3 and sampling == "420") else 8
+    mcux, mcuy = -(-w // mw), -(-h // mh)
+    outputs = []
+    for _ in range(int(rng.integers(1, 4))):
+        # strips of a random rectangle of the source, side by side in a random order (one strip: a crop; two: a swap)
+        nx, ny = int(rng.integers(1, mcux + 1)), int(rng.integers(1, mcuy + 1))
+        sx, sy = int(rng.integers(0, mcux - nx + 1)), int(rng.integers(0, mcuy - ny + 1))
+        cuts = sorted(set([0, nx] + [int(v) for v in rng.integers(1, nx + 1, int(rng.integers(0, 4)))]))
+        strips = [(a, b - a) for a, b in zip(cuts, cuts[1:])]
+        order = rng.permutation(len(strips))
+        regions, dx = [], 0
+        for i in order:
+            regions.append((sx + strips[i][0], sy, strips[i][1], ny, dx, 0))
+            dx += strips[i][1]
+        # the size: whole MCUs, or what the source shows of its last column and row, or any size inside the last MCUs
+        ow = min(nx * mw, w - sx * mw) if rng.random() < 0.7 else nx * mw - int(rng.integers(0, mw))
+        oh = min(ny * mh, h - sy * mh) if rng.random() < 0.7 else ny * mh - int(rng.integers(0, mh))
+        r = rng.random()
+        restart_out = None if r < 0.4 else 0 if r < 0.6 else 1 if r < 0.7 else int(rng.integers(1, nx * ny + 2))
+        outputs.append(dict(width=ow, height=oh, regions=regions, restart_mcus=restart_out, optimize=bool(rng.random() < 0.3)))
+    if refuse:
+        o = outputs[int(rng.integers(0, len(outputs)))]
+        if rng.random() < 0.5 or len(o["regions"]) == 1:
+            o["regions"] = o["regions"] + [o["regions"][0]]        # the first region twice: an overlap
+        else:
+            o["regions"] = o["regions"][:-1]                       # a strip is missing: uncovered MCUs (or a region outside the output)
+    KINDS["jpegxc"] = KINDS.get("jpegxc", 0) + 1
+    desc = f"JPEGXC {kind} {(h, w, cn)} seed={seed} quality={quality} sampling={sampling} {how} outputs={outputs!r}"
+    try:
+        want = XR.transcode(data, outputs)
+    except (XR.Unsupported, XR.Invalid) as e:
+        kind_of = NotImplementedError if isinstance(e, XR.Unsupported) else ValueError
+        try:
+            T.transcode_regions(data, outputs, device=dev)
+        except kind_of:
+            return desc + f" refused ({type(e).__name__})", 0
+        return desc + f" NOT refused ({type(e).__name__}: {e})", 1
+    got = T.transcode_regions(data, outputs, device=dev)
+    bad = sum(1 if len(a) != len(b) else int((np.frombuffer(a, np.uint8) != np.frombuffer(b, np.uint8)).sum()) for a, b in zip(got, want))
+    return desc, bad + abs(len(got) - len(want))
+
+
 def jpegdec_case(rng, dev) -> tuple[str, int]:
     """the device JPEG decoder (decode_jpeg_tensor) against its restatement (jpgdec_ref.decode), the pixels byte for byte: a random
     image up to 96 x 96 -- smooth, noise, flat, mixed -- written by Pillow (grey, 4:4:4, 4:2:2 or 4:2:0, any quality, optimised tables
@@ -1233,6 +1314,7 @@ def main() -> int:
     ap.add_argument("--jpegbatch", type=float, default=0.0, help="share of cases through the batched device JPEG encoder (encode_jpeg_tensors) against the single calls and jpg_ref.encode")
     ap.add_argument("--jpegopt", type=float, default=0.0, help="share of cases through the device JPEG encoder with optimised Huffman tables (optimize=True, single and batched) against jpg_opt_ref.encode")
     ap.add_argument("--jpegprog", type=float, default=0.0, help="share of cases through the device decoder of progressive JPEG files (decode_jpeg_tensor(progressive=True)) against jpgprog_ref.decode")
+    ap.add_argument("--jpegxc", type=float, default=0.0, help="share of cases through the lossless JPEG transcoder (transcode_regions: crops, splits, swaps) against jpgxc_ref.transcode")
     ap.add_argument("--cases", type=int, default=None, help="stop after this many cases (before --seconds runs out)")
     ap.add_argument("--feat", type=float, default=0.0, help="share of cases through the feature pipeline (features.detect / features.match) against tests/feat_ref.py")
     ap.add_argument("--only", type=int, default=None, help="run only this case number (reproduce)")
@@ -1267,12 +1349,14 @@ def main() -> int:
             r_kind = rng.random()
             wide_chain = False
             counted = True
-            top = 1.0 - a.jpegprog - a.jpegopt - a.jpegbatch - a.jpegdec
-            if r_kind >= 1.0 - a.jpegprog:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+            top = 1.0 - a.jpegxc - a.jpegprog - a.jpegopt - a.jpegbatch - a.jpegdec
+            if r_kind >= 1.0 - a.jpegxc:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+                desc, bad = jpegxc_case(rng, dev)
+            elif r_kind >= 1.0 - a.jpegxc - a.jpegprog:
                 desc, bad = jpegprog_case(rng, dev)
-            elif r_kind >= 1.0 - a.jpegprog - a.jpegopt:
+            elif r_kind >= 1.0 - a.jpegxc - a.jpegprog - a.jpegopt:
                 desc, bad = jpegopt_case(rng, dev)
-            elif r_kind >= 1.0 - a.jpegprog - a.jpegopt - a.jpegbatch:
+            elif r_kind >= 1.0 - a.jpegxc - a.jpegprog - a.jpegopt - a.jpegbatch:
                 desc, bad = jpegbatch_case(rng, dev)
             elif r_kind >= top:
                 desc, bad = jpegdec_case(rng, dev)

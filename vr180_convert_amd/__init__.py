@@ -23,6 +23,7 @@ from .jpeg_device import (encode_jpeg_tensor, encode_jpeg_tensors, imwrite_jpeg_
                           last_encode_batch_report)
 from .jpeg_decode_device import (decode_jpeg_tensor, decode_jpeg_tensors, imread_tensor, imread_tensors, last_batch_report,
                                  last_decode_report)
+from .jpeg_transcode_device import split_sbs_jpeg, swap_sbs_jpeg, transcode_jpeg
 from .sharding import remap_sharded
 
 __all__ = [
@@ -69,4 +70,8 @@ __all__ = [
     "decode_jpeg_tensors",
     "imread_tensors",
     "last_batch_report",
+    # lossless crop, split and swap of JPEG files in the DCT domain, on the device (swap --lossless, xmp --device)
+    "transcode_jpeg",
+    "split_sbs_jpeg",
+    "swap_sbs_jpeg",
 ]

@@ -28,6 +28,7 @@ SYMBOLS = [
     "v1c_jpeg_decode_info", "v1c_jpeg_decode", "v1c_jpeg_decode_batch",
     "v1c_jpeg_header_opt", "v1c_jpeg_encode_opt", "v1c_jpeg_encode_batch_opt",
     "v1c_jpeg_prog_info", "v1c_jpeg_prog_decode",
+    "v1c_jpeg_transcode_bound", "v1c_jpeg_transcode_check", "v1c_jpeg_header_xc", "v1c_jpeg_transcode",
 ]
 
 
@@ -119,6 +120,15 @@ def lib() -> C.CDLL:
     try:
         L.v1c_jpeg_prog_info.argtypes = [C.c_char_p, C.c_uint64, vp]
         L.v1c_jpeg_prog_decode.argtypes = [i32, vp, C.c_char_p, C.c_uint64, vp, i64, i32, C.c_uint32, vp, vp, C.c_uint32]
+    except AttributeError:  # (an older build behind V1C_LIB)
+        pass
+    try:
+        L.v1c_jpeg_transcode_bound.argtypes = [C.c_char_p, C.c_uint64, i32, i32, i32]
+        L.v1c_jpeg_transcode_bound.restype = C.c_uint64
+        L.v1c_jpeg_transcode_check.argtypes = [C.c_char_p, C.c_uint64, i32, vp, vp]
+        L.v1c_jpeg_header_xc.argtypes = [C.c_char_p, C.c_uint64, i32, i32, i32, vp, C.c_uint32, vp, C.c_uint64]
+        L.v1c_jpeg_header_xc.restype = i64
+        L.v1c_jpeg_transcode.argtypes = [i32, vp, C.c_char_p, C.c_uint64, i32, vp, C.c_uint32, vp]
     except AttributeError:  # (an older build behind V1C_LIB)
         pass
     L.v1c_plan_run.argtypes = [vp, vp, C.POINTER(_abi.Unit), i32]

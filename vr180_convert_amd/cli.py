@@ -228,6 +228,9 @@ def lr(
     device_decode_progressive: Annotated[bool, typer.Option("--device-decode-progressive", help="With --device-decode or --device-decode-batch: "
                                                                                                  "progressive JPEG inputs are decoded on "
                                                                                                  "the GPU too")] = False,
+    device_vr180: Annotated[bool, typer.Option("--device-vr180", help="Write a .jpg / .jpeg result as a Google VR180 photo: both eyes "
+                                                                       "encoded on the GPU, the right eye embedded in the left eye's "
+                                                                       "XMP (not with --merge)")] = False,
 ) -> None:
     """Remap a pair of fisheye images to a pair of SBS equirectangular images."""
     from .remapper import apply_lr
@@ -263,7 +266,8 @@ def lr(
         LOG.info(f"Automatched transformer: {chain}")
     apply_lr(chain, left_path=left_in, right_path=right_in, out_path=out, radius=radius_, size_output=parse_size(size),
              interpolation=interp, boarder_mode=border, boarder_value=border_value, merge=merge,
-             **({"device_png": True} if device_png else {}), **({"device_jpeg": "batch"} if device_jpeg_batch else {"device_jpeg": True} if device_jpeg else {}),
+             **({"device_png": True} if device_png else {}),
+             **({"device_jpeg": "vr180"} if device_vr180 else {"device_jpeg": "batch"} if device_jpeg_batch else {"device_jpeg": True} if device_jpeg else {}),
              **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}),
              **({"device_jpeg_optimize": True} if device_jpeg_optimize else {}),
              **({"device_decode_progressive": True} if device_decode_progressive else {}))
@@ -320,9 +324,26 @@ def s(
 def swap(
     in_paths: Annotated[List[Path], typer.Argument(help="Image paths")],
     overwrite: Annotated[bool, typer.Option(help="Overwrite the original images")] = True,
+    lossless: Annotated[bool, typer.Option("--lossless", help="Exchange the halves of .jpg / .jpeg files in the DCT domain on the GPU: "
+                                                               "no pixel changes, no JPEG generation is lost (the halves must be whole "
+                                                               "MCUs wide; other files are decoded and encoded again as without it)")] = False,
 ) -> None:
     """Swap the left and right halves of side-by-side images."""
     for p in in_paths:
+        if lossless and p.suffix.lower() in (".jpg", ".jpeg"):
+            from . import jpeg_transcode_device as _xc
+
+            from .jpeg_decode_device import CorruptJPEG
+
+            try:
+                swapped = _xc.swap_sbs_jpeg(p.read_bytes())
+            except CorruptJPEG as e:  # a damaged file has no other route: said here, where the message names the byte
+                raise typer.BadParameter(f"{p}: {e}") from e
+            except (NotImplementedError, ValueError) as e:  # outside the transcoder's scope, or halves off the MCU grid: said, then as ever
+                LOG.warning(f"--lossless: {p} is decoded and encoded again: {e}")
+            else:
+                (p if overwrite else p.with_suffix(f".swap{p.suffix}")).write_bytes(swapped)
+                continue
         image = _io.imread(p)
         if image is None:
             raise ValueError(f"cannot read {p}")
@@ -334,9 +355,12 @@ def swap(
 def xmp(
     in_paths: Annotated[List[Path], typer.Argument(help="Side-by-side image paths")],
     wslpath: Annotated[bool, typer.Option("-wsl", "--wslpath", help="Convert Windows paths to WSL paths (runs `wslpath`)")] = False,
+    device: Annotated[bool, typer.Option("--device", help="Split .jpg / .jpeg files in the DCT domain on the GPU and write the XMP "
+                                                           "here: no pixel changes, no libxmp (the halves must be whole MCUs wide; "
+                                                           "other files take the route without it)")] = False,
 ) -> None:
     """Write the left half as <name>.xmp<ext> with the right half embedded as Google VR180 photo metadata
-    (GPano / GImage XMP, cli.py:439-540).  Needs python-xmp-toolkit (libxmp / exempi)."""
+    (GPano / GImage XMP, cli.py:439-540).  Needs python-xmp-toolkit (libxmp / exempi) unless --device takes the file."""
     import subprocess as sp
 
     from . import calibration_cv as _cvx
@@ -344,6 +368,24 @@ def xmp(
     for in_path in in_paths:
         if wslpath:  # cli.py:477-482
             in_path = Path(sp.run(["wslpath", "-u", "-a", str(in_path)], capture_output=True).stdout.decode().strip())  # noqa: S603, S607
+        if device and in_path.suffix.lower() in (".jpg", ".jpeg"):
+            from . import jpeg_transcode_device as _xc, vr180_photo as _vp
+
+            from .jpeg_decode_device import CorruptJPEG
+
+            try:
+                data = in_path.read_bytes()  # (read once: the size and the split take the bytes)
+                height, width, _, _ = _xc.probe_mcu(data)
+                left, right = _xc.split_sbs_jpeg(data)
+            except CorruptJPEG as e:  # a damaged file has no other route: said here, where the message names the byte
+                raise typer.BadParameter(f"{in_path}: {e}") from e
+            except (NotImplementedError, ValueError) as e:  # outside the transcoder's scope, or halves off the MCU grid: said, then as ever
+                LOG.warning(f"--device: {in_path} takes the host route: {e}")
+            else:
+                written = in_path.with_suffix(f".xmp{in_path.suffix}")
+                written.write_bytes(_vp.assemble_vr180_photo(left, right, width, height))
+                LOG.info(f"Saved {written}")
+                continue
         try:
             written = _cvx.write_vr180_xmp(in_path)
         except _cvx.OptionalDependencyMissing as e:

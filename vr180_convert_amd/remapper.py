@@ -1009,7 +1009,7 @@ def apply_lr(
     merge: bool = False,
     device: Any = None,
     device_png: bool = False,
-    device_jpeg: bool | Literal["batch"] = False,
+    device_jpeg: bool | Literal["batch", "vr180"] = False,
     device_decode: bool | Literal["batch"] = False,
     device_jpeg_optimize: bool = False,
     device_decode_progressive: bool = False,
@@ -1022,13 +1022,21 @@ def apply_lr(
     ``device_jpeg=True``: the same for a ``.jpg`` / ``.jpeg`` ``out_path`` of a uint8 result (jpeg_device.imwrite_jpeg_tensor:
     quality 95, 4:2:0, as the host writer).  ``device_jpeg="batch"``: accepted as in ``apply``; the side-by-side frame is a batch of
     one (jpeg_device.imwrite_jpeg_tensors), the same bytes.  ``device_jpeg_optimize=True``: with either mode, the file gets Huffman
-    tables built for the image on the device (``optimize=True`` of jpeg_device.py).
+    tables built for the image on the device (``optimize=True`` of jpeg_device.py).  ``device_jpeg="vr180"``: the result is written as a
+    Google VR180 photo instead of a side-by-side frame -- the two halves are encoded on the device as a batch of two and the right eye
+    is embedded in the left eye's XMP (vr180_photo.imwrite_vr180_tensor); ``ValueError`` with ``merge=True`` or for a result the
+    device encoder does not take.
     ``device_decode=True``: ``.jpg`` / ``.jpeg`` inputs are decoded on the device (jpeg_decode_device.py) and only their bytes are
     uploaded; one file holding both eyes is decoded once and the halves are views of it.  Files outside the device decoder's scope
     are read by the host as before.  ``device_decode="batch"``: the same, with the two files decoded as one batch of two.
     ``device_decode_progressive=True``: with either mode, progressive JPEG inputs are decoded on the device too instead of going to the
     host reader (``progressive=True`` of jpeg_decode_device.py)."""
-    device_jpeg = _device_jpeg_mode(device_jpeg)
+    vr180 = isinstance(device_jpeg, str) and device_jpeg == "vr180"
+    device_jpeg = True if vr180 else _device_jpeg_mode(device_jpeg)
+    if vr180 and merge:
+        raise ValueError('device_jpeg="vr180" writes the two eyes: it does not go with merge=True')
+    if vr180 and not (isinstance(out_path, (str, Path)) and Path(out_path).suffix.lower() in (".jpg", ".jpeg")):
+        raise ValueError(f'device_jpeg="vr180" takes a .jpg / .jpeg out_path, not {out_path}')  # (before anything is read or remapped)
     jpeg_kw = {"optimize": True} if device_jpeg_optimize else {}
     if device_decode:
         if isinstance(left_path, (str, Path)) and isinstance(right_path, (str, Path)) and left_path == right_path:
@@ -1065,7 +1073,7 @@ def apply_lr(
         w = size_output[0]
         combine = _io.draw_anaglyph_labels(anaglyph_tensors(sbs[:, :w], sbs[:, w:]).cpu().numpy())
     else:
-        if device_png and out_path is not None:
+        if device_png and out_path is not None and not vr180:
             from . import png_device
 
             if png_device.eligible(out_path, sbs):
@@ -1075,8 +1083,14 @@ def apply_lr(
         if device_jpeg and out_path is not None:
             from . import jpeg_device
 
+            if vr180 and not jpeg_device.eligible(out_path, sbs):
+                raise ValueError(f'device_jpeg="vr180" takes a .jpg / .jpeg out_path and a uint8 result, not {out_path} and {sbs.dtype}')
             if jpeg_device.eligible(out_path, sbs):
-                if device_jpeg == "batch":
+                if vr180:
+                    from . import vr180_photo
+
+                    vr180_photo.imwrite_vr180_tensor(out_path, sbs, **jpeg_kw)
+                elif device_jpeg == "batch":
                     jpeg_device.imwrite_jpeg_tensors([out_path], [sbs], **jpeg_kw)
                 else:
                     jpeg_device.imwrite_jpeg_tensor(out_path, sbs, **jpeg_kw)
