@@ -631,6 +631,67 @@ int64_t v1c_jpeg_header_xc(const uint8_t* file, uint64_t size, int width, int he
 int v1c_jpeg_transcode(int device, void* stream, const uint8_t* file, uint64_t size, int n, v1c_jpeg_xc_output* outputs,
                        uint32_t subseq_bits, v1c_jpeg_decode_report* report);
 
+/* ---- lossless JPEG join, rotate and flip (INTEGRATION.md section 10 states the contract; tests/jpgxf_ref.py restates it) -------------
+ * v1c_jpeg_transcode with up to V1C_JPEG_XF_MAX_SOURCES files and a transform per region.  A region is nx x ny MCUs of file `source`
+ * from MCU (src_x, src_y), transformed and placed with the first MCU of the RESULT at MCU (dst_x, dst_y) of the output.  A transform is
+ * three bits -- 4: transpose first, 1: then mirror x, 2: then mirror y --, so 0 none, 1 flip_h, 2 flip_v, 3 rot180, 4 transpose, 5
+ * rot90 (clockwise), 6 rot270, 7 transverse.  MCUs move within the region, luma blocks within the MCU, coefficients within the block,
+ * and coefficients of odd frequency along a mirrored axis change sign; no magnitude changes.  A region is placed as NX x NY MCUs:
+ * nx x ny, or ny x nx where it transposes.  A transform acts on whole MCUs: what a partial last MCU column or row holds beyond the
+ * image's edge moves with it.
+ * Every source must be a file v1c_jpeg_transcode takes (its codes otherwise).  V1C_E_UNSUPPORTED for sources of different component
+ * counts or sampling factors; for a transposing code on a file with h_samp != v_samp (4:2:2: the result would be 4:4:0); for regions
+ * of an output whose effective quantisation tables -- the source's, transposed where the region transposes -- are not region 0's; and
+ * for regions that overlap in an output.  V1C_E_INVALID for every other rule of the regions -- a source or transform out of range,
+ * outside the source, the placed rectangle outside the output, an MCU of the output uncovered, more than
+ * V1C_JPEG_XC_MAX_REGIONS of them --, for sizes, restart_mcus, capacity, and for nsources or n out of range.  All before any device
+ * call.                                                                                                                           */
+#define V1C_JPEG_XF_MAX_SOURCES 4
+
+typedef struct v1c_jpeg_xf_source {
+    const uint8_t* file;              /* HOST memory                                                                             */
+    uint64_t size;
+} v1c_jpeg_xf_source;
+
+typedef struct v1c_jpeg_xf_region {   /* in MCUs                                                                                  */
+    int32_t source, transform, src_x, src_y, nx, ny, dst_x, dst_y;
+} v1c_jpeg_xf_region;
+
+typedef struct v1c_jpeg_xf_output {   /* v1c_jpeg_xc_output with v1c_jpeg_xf_region regions                                       */
+    int32_t width, height;
+    int32_t restart_mcus;
+    int32_t optimize;
+    int32_t nregions, reserved;
+    const v1c_jpeg_xf_region* regions;
+    uint8_t* out_host;
+    uint64_t capacity;                /* >= v1c_jpeg_compose_bound of this output                                                */
+    uint64_t size;
+    uint32_t dht_size;
+    uint8_t dht[V1C_JPEG_DHT_MAX];
+} v1c_jpeg_xf_output;
+
+/* v1c_jpeg_transcode_bound for an output of files like `file` (any of the sources: the bound depends on the components and the
+ * sampling factors alone).  Host-only.                                                                                            */
+uint64_t v1c_jpeg_compose_bound(const uint8_t* file, uint64_t size, int width, int height, int restart_mcus);
+
+/* Every check of v1c_jpeg_compose that needs no device, and nothing else.  Touches no device.  error_pos (may be NULL): nsources
+ * entries, where each source's parse stopped.                                                                                     */
+int v1c_jpeg_compose_check(int nsources, const v1c_jpeg_xf_source* sources, int n, const v1c_jpeg_xf_output* outputs, uint64_t* error_pos);
+
+/* v1c_jpeg_header_xc with the file's quantisation tables transposed where `transposed` is not 0: the header of an output whose
+ * region 0 is of this file and transposes or not.  Host-only.                                                                     */
+int64_t v1c_jpeg_header_xf(const uint8_t* file, uint64_t size, int width, int height, int restart_mcus, int transposed, const uint8_t* dht,
+                           uint32_t dht_size, uint8_t* out, uint64_t capacity);
+
+/* Composes n outputs from nsources files (HOST memory) on `stream`, as v1c_jpeg_transcode does from one.  Each source is decoded in
+ * turn up to its DC scan into a coefficient store of its own; the stream is SYNCHRONISED once per round of each decode, once per
+ * call for the verdicts -- every source's entropy-coded data and the range of the gathered coefficients --, and twice for the sizes
+ * and the scans.  reports (may be NULL): nsources entries, one per source; after V1C_E_CORRUPT from the device the damaged source's
+ * error_pos is the bit, the others' 0.  V1C_E_UNSUPPORTED, before anything is done on the device, while `stream` is being
+ * captured.                                                                                                                       */
+int v1c_jpeg_compose(int device, void* stream, int nsources, const v1c_jpeg_xf_source* sources, int n, v1c_jpeg_xf_output* outputs,
+                     uint32_t subseq_bits, v1c_jpeg_decode_report* reports);
+
 #ifdef __cplusplus
 }
 #endif

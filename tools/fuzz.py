@@ -7,7 +7,7 @@ and destination views (dword-aligned or not), per-unit rotations, apply_lr pairs
 (v1c_remap_lut) on random float32 maps sprinkled with NaN, infinities, 2^15 / 2^26 / 2^31-scale values and ties of the 1/32 grid.
 
     python3 tools/fuzz.py [--seconds 300] [--seed 1] [--big 0.15] [--lut 0.15] [--hot 0.3] [--gen2 0] [--api 0.1] [--auto 0.06] [--fused 0.06] [--log gpurun_out/fuzz.log]
-                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--jpegprog 0] [--jpegxc 0] [--cases N]
+                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--jpegprog 0] [--jpegxc 0] [--jpegxf 0] [--cases N]
 
 --wide P: that share of the cases has uint16 or float32 pixels (k_remap_wide): the chain cases above -- same grammar, views, batches, pairs,
 per-unit rotations, graph replays and the same three masks, counted in the same counters -- and the LUT cases (v1c_remap_lut_ex, nothing left
@@ -28,7 +28,7 @@ scale, radius, margin, threshold, cell, per_cell and the cap drawn off their def
 sets of 0 ... 20000 descriptors with planted copies, duplicates and ties.  A case that v1c_feat_detect refuses (working image under 33 x 33, empty
 circle) where feat_ref.refusal predicts it is correct and not counted (the summary line says how many).  --jpegprog P: that share goes through the device decoder of progressive JPEG files
 (decode_jpeg_tensor(progressive=True)) -- Pillow's progressive files and tests/jpgprog_cases.py's writer with random legal scan scripts --
-against tests/jpgprog_ref.py: pixels, scans and the rounds of every scan.  These shares come off the top of the
+against tests/jpgprog_ref.py: pixels, scans and the rounds of every scan.  --jpegxf P: that share goes through the lossless JPEG composer (compose_regions) -- one to four random files of one kind up to 96 x 96 and one or two outputs of strips under random codes -- against tests/jpgxf_ref.py, byte for byte; a composition both sides refuse alike counts as agreement (the summary line says how many).  These shares come off the top of the
 case draw: with all of them at 0 every earlier seed replays as it ran.
 
 Round 5 added to the grammar: hot shapes of the chains that left the interpreter (planar fisheye -> fisheye, is_latitude_y=False, a
@@ -172,6 +172,7 @@ GEN2 = [0.0]  # share of the chain cases forced into general mode 2 (--gen2)
 KINDS: dict = {}  # kernel family -> launch groups it served (remapper.last_launch_kinds): which kernels the run reached
 SINGULAR = [0]  # differing pixels among the ill-conditioned ones that are left out (module docstring)
 TIES = [0]  # ... among those at a float32 rounding tie (float32_ties)
+XF = {"drawn": 0, "refused": 0}  # compositions of the --jpegxf share, and those of them the restatement refuses
 LAST_MASKED = [0.0]  # share of the last chain case's pixels that its masks left out (the largest over its units)
 WIDE_CHAIN = {"run": 0, "not counted": 0, "masked px": 0, "px": 0}  # chain cases of --wide: a case with more than 5 % masked is not counted
 
@@ -1019,6 +1020,102 @@ def jpegxc_case(rng, dev) -> tuple[str, int]:
     return desc, bad + abs(len(got) - len(want))
 
 
+def jpegxf_draw(rng) -> tuple[list, list, str]:
+    """a random composition: one to four files of one kind -- grey, 4:4:4, 4:2:2 or 4:2:0, up to 96 x 96, one quality (now and then one of
+    them another), written by Pillow or by the encoder's restatement with any restart interval -- and one or two outputs, each a row of
+    one to four strips, every strip a random rectangle of a random source under a random code, all of one height as they are placed;
+    the strips of an output all transpose or none does (now and then they mix, which only symmetric tables allow); now and then a
+    strip is doubled or dropped, which must be refused.  No device is touched: the draw is the same wherever it runs."""
+    import jpg_cases as JC
+    import jpg_ref as JR
+    import jpgdec_cases as DC
+
+    cn = 1 if rng.random() < 0.2 else 3
+    sampling = str(rng.choice(["420", "420", "444", "422"]))
+    mw = 8 if cn == 1 else {"444": 8, "422": 16, "420": 16}[sampling]
+    mh = 16 if (cn == 3 and sampling == "420") else 8
+    quality = int(rng.choice([50, 75, 90, 95, 100]))
+    datas, grids, hows = [], [], []
+    for _ in range(int(rng.integers(1, 5))):
+        h, w = (int(v) for v in rng.integers(1, 97, 2))
+        seed = int(rng.integers(0, 1 << 30))
+        img = np.ascontiguousarray(JC.noise(h, w, cn, seed) if rng.random() < 0.3 else JC.smooth(h, w, cn, seed))
+        q = quality if rng.random() < 0.96 else int(rng.integers(1, 101))
+        if sampling != "422" and rng.random() < 0.4:
+            restart = int(rng.integers(1, -(-h // mh) * -(-w // mw) + 2))
+            datas.append(JR.encode(img, q, sampling, restart))
+            hows.append(f"{(h, w)} seed={seed} q={q} jpg_ref restart_mcus={restart}")
+        else:
+            datas.append(DC.pillow(img, q, sampling))
+            hows.append(f"{(h, w)} seed={seed} q={q} Pillow")
+        grids.append((-(-w // mw), -(-h // mh)))
+    square = mw == mh
+    outputs = []
+    for _ in range(int(rng.integers(1, 3))):
+        transposing = square and rng.random() < 0.5
+        mixed = square and rng.random() < 0.1
+        H = int(rng.integers(1, min(min(g) for g in grids) + 1))
+        regions, dx = [], 0
+        for _ in range(int(rng.integers(1, 5))):
+            si = int(rng.integers(0, len(datas)))
+            t = bool(rng.integers(0, 2)) if mixed else transposing
+            code = int(rng.integers(0, 4)) | (4 if t else 0)
+            mcux, mcuy = grids[si]
+            if t:
+                nx, ny = H, int(rng.integers(1, mcuy + 1))
+            else:
+                nx, ny = int(rng.integers(1, mcux + 1)), H
+            sx, sy = int(rng.integers(0, mcux - nx + 1)), int(rng.integers(0, mcuy - ny + 1))
+            regions.append((si, code, sx, sy, nx, ny, dx, 0))
+            dx += ny if t else nx
+        ow = dx * mw - (0 if rng.random() < 0.6 else int(rng.integers(0, mw)))
+        oh = H * mh - (0 if rng.random() < 0.6 else int(rng.integers(0, mh)))
+        r = rng.random()
+        restart_out = None if r < 0.4 else 0 if r < 0.6 else 1 if r < 0.7 else int(rng.integers(1, dx * H + 2))
+        outputs.append(dict(width=ow, height=oh, regions=regions, restart_mcus=restart_out, optimize=bool(rng.random() < 0.3)))
+    if rng.random() < 0.08:
+        o = outputs[int(rng.integers(0, len(outputs)))]
+        if rng.random() < 0.5 or len(o["regions"]) == 1:
+            o["regions"] = o["regions"] + [o["regions"][0]]        # the first strip twice: an overlap
+        else:
+            o["regions"] = o["regions"][:-1]                       # the last strip is missing: uncovered MCUs
+    return datas, outputs, f"JPEGXF cn={cn} sampling={sampling} sources=[{'; '.join(hows)}] outputs={outputs!r}"
+
+
+def jpegxf_reference(datas, outputs):
+    """(files, None) of the restatement (tests/jpgxf_ref.py), or (None, the exception it refuses the composition with)"""
+    import jpgxf_ref as FR
+
+    try:
+        return FR.compose(datas, outputs), None
+    except (FR.Unsupported, FR.Invalid) as e:
+        return None, e
+
+
+def jpegxf_case(rng, dev) -> tuple[str, int]:
+    """the lossless JPEG composer (jpeg_compose_device.compose_regions) against its restatement (jpgxf_ref.compose), the files byte
+    for byte; a composition the restatement refuses must be refused its way, which counts as agreement (the summary line says how many)"""
+    import jpgxf_ref as FR
+    from vr180_convert_amd import jpeg_compose_device as T
+
+    datas, outputs, desc = jpegxf_draw(rng)
+    named = [dict(o, regions=[(r[0], FR.NAMES[r[1]]) + tuple(r[2:]) for r in o["regions"]]) for o in outputs]
+    KINDS["jpegxf"] = KINDS.get("jpegxf", 0) + 1
+    XF["drawn"] += 1
+    want, e = jpegxf_reference(datas, outputs)
+    if e is not None:
+        XF["refused"] += 1
+        kind_of = NotImplementedError if isinstance(e, FR.Unsupported) else ValueError
+        try:
+            T.compose_regions(datas, named, device=dev)
+        except kind_of:
+            return desc + f" refused ({type(e).__name__})", 0
+        return desc + f" NOT refused ({type(e).__name__}: {e})", 1
+    got = T.compose_regions(datas, named, device=dev)
+    bad = sum(1 if len(a) != len(b) else int((np.frombuffer(a, np.uint8) != np.frombuffer(b, np.uint8)).sum()) for a, b in zip(got, want))
+    return desc, bad + abs(len(got) - len(want))
+
+
 def jpegdec_case(rng, dev) -> tuple[str, int]:
     """the device JPEG decoder (decode_jpeg_tensor) against its restatement (jpgdec_ref.decode), the pixels byte for byte: a random
     image up to 96 x 96 -- smooth, noise, flat, mixed -- written by Pillow (grey, 4:4:4, 4:2:2 or 4:2:0, any quality, optimised tables
@@ -1315,6 +1412,7 @@ def main() -> int:
     ap.add_argument("--jpegopt", type=float, default=0.0, help="share of cases through the device JPEG encoder with optimised Huffman tables (optimize=True, single and batched) against jpg_opt_ref.encode")
     ap.add_argument("--jpegprog", type=float, default=0.0, help="share of cases through the device decoder of progressive JPEG files (decode_jpeg_tensor(progressive=True)) against jpgprog_ref.decode")
     ap.add_argument("--jpegxc", type=float, default=0.0, help="share of cases through the lossless JPEG transcoder (transcode_regions: crops, splits, swaps) against jpgxc_ref.transcode")
+    ap.add_argument("--jpegxf", type=float, default=0.0, help="share of cases through the lossless JPEG composer (compose_regions: joins, rotations, flips of up to four files) against jpgxf_ref.compose")
     ap.add_argument("--cases", type=int, default=None, help="stop after this many cases (before --seconds runs out)")
     ap.add_argument("--feat", type=float, default=0.0, help="share of cases through the feature pipeline (features.detect / features.match) against tests/feat_ref.py")
     ap.add_argument("--only", type=int, default=None, help="run only this case number (reproduce)")
@@ -1349,14 +1447,17 @@ def main() -> int:
             r_kind = rng.random()
             wide_chain = False
             counted = True
-            top = 1.0 - a.jpegxc - a.jpegprog - a.jpegopt - a.jpegbatch - a.jpegdec
-            if r_kind >= 1.0 - a.jpegxc:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+            rest = 1.0 - a.jpegxf
+            top = rest - a.jpegxc - a.jpegprog - a.jpegopt - a.jpegbatch - a.jpegdec
+            if r_kind >= rest:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+                desc, bad = jpegxf_case(rng, dev)
+            elif r_kind >= rest - a.jpegxc:
                 desc, bad = jpegxc_case(rng, dev)
-            elif r_kind >= 1.0 - a.jpegxc - a.jpegprog:
+            elif r_kind >= rest - a.jpegxc - a.jpegprog:
                 desc, bad = jpegprog_case(rng, dev)
-            elif r_kind >= 1.0 - a.jpegxc - a.jpegprog - a.jpegopt:
+            elif r_kind >= rest - a.jpegxc - a.jpegprog - a.jpegopt:
                 desc, bad = jpegopt_case(rng, dev)
-            elif r_kind >= 1.0 - a.jpegxc - a.jpegprog - a.jpegopt - a.jpegbatch:
+            elif r_kind >= rest - a.jpegxc - a.jpegprog - a.jpegopt - a.jpegbatch:
                 desc, bad = jpegbatch_case(rng, dev)
             elif r_kind >= top:
                 desc, bad = jpegdec_case(rng, dev)
@@ -1407,7 +1508,8 @@ def main() -> int:
         + (f", {TIES[0]} at float32 rounding ties" if TIES[0] else "")
         + (f"; wide chain cases: {WIDE_CHAIN['run']} run, {WIDE_CHAIN['not counted']} of them over 5 % masked and not counted, "
            f"{WIDE_CHAIN['masked px']} of {WIDE_CHAIN['px']} pixels masked" if WIDE_CHAIN["run"] else "")
-        + (f"; feat cases: {FEAT['drawn']} drawn, {FEAT['refused']} of them refused as predicted and not counted" if FEAT["drawn"] else ""))
+        + (f"; feat cases: {FEAT['drawn']} drawn, {FEAT['refused']} of them refused as predicted and not counted" if FEAT["drawn"] else "")
+        + (f"; jpegxf cases: {XF['drawn']} drawn, {XF['refused']} of them refused by both sides alike" if XF["drawn"] else ""))
     say("kernel families of the chain cases' launch groups: " + ", ".join(f"{k} x{v}" for k, v in sorted(KINDS.items())))
     return 1 if n_bad else 0
 

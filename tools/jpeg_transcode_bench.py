@@ -12,7 +12,14 @@ decode; path (b) three times.  Generation loss: the PSNR of Pillow's pixels of e
 source (infinite where every sample is the same).  The size of the transcoder's files with the Annex K tables and with
 ``optimize=True``.  One JSON line per (file, job); ``--out`` appends them to a file.
 
+With ``--transform OP`` (repeatable) and ``--join`` the jobs are the composer's instead (jpeg_compose_device.transform_jpeg,
+join_sbs_jpeg): the whole file flipped or rotated, and the join of its two halves (split beforehand, outside the clocks), against
+(a) ``decode_jpeg_tensor``, a torch flip / transpose, ``encode_jpeg_tensor`` and (b) Pillow's ``transpose`` / ``hstack``; the PSNR is
+taken after the pixels are turned back.  A job ``whole`` -- ``transcode_jpeg`` of the same file, whose gather is ``k_jxc_gather`` over the
+same blocks -- runs beside them, so that one profiler session holds both gathers.
+
     python tools/jpeg_transcode_bench.py --out profiles/jpeg_transcode/bench.jsonl
+    python tools/jpeg_transcode_bench.py --transform rot180 --transform rot90 --join --out profiles/jpeg_compose/bench.jsonl
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/jpeg_transcode_bench.py --runs 2 --device-only     (per-kernel times)
 """
 from __future__ import annotations
@@ -80,17 +87,54 @@ def _save(arr: np.ndarray, sampling: int) -> bytes:
     return b.getvalue()
 
 
+def compose_jobs(V, data: bytes, w: int, sampling: int, sub: str, transforms: list, join: bool) -> dict:
+    """job: (the composer's call, the device codecs' path, Pillow's path, the pixels of the made files turned back to the source's)"""
+    from PIL import Image
+
+    from vr180_convert_amd.jpeg_compose_device import TRANSFORMS
+
+    def turned(x, code, flip, swap):  # transpose first, then mirror x, then mirror y
+        if code & 4:
+            x = swap(x)
+        if code & 1:
+            x = flip(x, 1)
+        if code & 2:
+            x = flip(x, 0)
+        return x
+
+    inverse = {0: 0, 1: 1, 2: 2, 3: 3, 4: 4, 5: 6, 6: 5, 7: 7}
+    jobs = {"whole": (lambda **kw: [V.transcode_jpeg(data, **kw)],
+                      lambda: [V.encode_jpeg_tensor(V.decode_jpeg_tensor(data), quality=95, subsampling=sub)],
+                      lambda: [_save(_pixels(data), sampling)], lambda px: px[0])}
+    for op in transforms:
+        code = TRANSFORMS[op]
+        jobs[op] = (lambda op=op, **kw: [V.transform_jpeg(data, op, **kw)],
+                    lambda code=code: [V.encode_jpeg_tensor(turned(V.decode_jpeg_tensor(data), code, lambda x, d: x.flip(d), lambda x: x.transpose(0, 1)).contiguous(),
+                                                            quality=95, subsampling=sub)],
+                    lambda code=code: [_save(np.ascontiguousarray(turned(_pixels(data), code, lambda x, d: np.flip(x, d), lambda x: np.swapaxes(x, 0, 1))), sampling)],
+                    lambda px, code=code: turned(px[0], inverse[code], lambda x, d: np.flip(x, d), lambda x: np.swapaxes(x, 0, 1)))
+    if join:
+        left, right = V.split_sbs_jpeg(data)
+        jobs["join"] = (lambda **kw: [V.join_sbs_jpeg(left, right, **kw)],
+                        lambda: [V.encode_jpeg_tensor(torch.cat([V.decode_jpeg_tensor(left), V.decode_jpeg_tensor(right)], dim=1), quality=95, subsampling=sub)],
+                        lambda: [_save(np.ascontiguousarray(np.hstack([_pixels(left), _pixels(right)])), sampling)], lambda px: px[0])
+    return jobs
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("files", nargs="*", help="side-by-side JPEG files (default: the docs image and an 8192 x 4096 sphere scene)")
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--device-only", action="store_true", help="the transcoder and path (a) only, no PSNR (profiler runs)")
+    ap.add_argument("--transform", action="append", default=[], metavar="OP", help="the composer's jobs instead: the whole file under OP (repeatable)")
+    ap.add_argument("--join", action="store_true", help="the composer's jobs instead: the join of the file's two halves")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("jpeg_transcode_bench needs the MI355X")
     import vr180_convert_amd as V
     from vr180_convert_amd import jpeg_transcode_device as T
+    from vr180_convert_amd.jpeg_compose_device import last_compose_report
 
     files = {Path(f).name: Path(f).read_bytes() for f in a.files} if a.files else default_files()
     for name, data in files.items():
@@ -120,9 +164,11 @@ def main() -> None:
                           lambda px: np.hstack(px)),
                 "swap": (lambda **kw: [V.swap_sbs_jpeg(data, **kw)], codecs_swap, pillow_swap,
                          lambda px: np.hstack([px[0][:, w // 2:], px[0][:, :w // 2]]))}
+        if a.transform or a.join:
+            jobs = compose_jobs(V, data, w, sampling, sub, a.transform, a.join)
         for job, (xc, codecs, pillow, back) in jobs.items():
             made = xc()  # warm-up: code objects, the page-locked buffer, the memory pool
-            rounds = T.last_transcode_report()["rounds"]
+            rounds = T.last_transcode_report()["rounds"] if job in ("split", "swap", "whole") else [r["rounds"] for r in last_compose_report()["sources"]]
             via = codecs()
             dec_rounds = V.last_decode_report()["rounds"]
             torch.cuda.synchronize()

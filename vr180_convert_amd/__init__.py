@@ -24,6 +24,8 @@ from .jpeg_device import (encode_jpeg_tensor, encode_jpeg_tensors, imwrite_jpeg_
 from .jpeg_decode_device import (decode_jpeg_tensor, decode_jpeg_tensors, imread_tensor, imread_tensors, last_batch_report,
                                  last_decode_report)
 from .jpeg_transcode_device import split_sbs_jpeg, swap_sbs_jpeg, transcode_jpeg
+from .jpeg_compose_device import (compose_regions, join_sbs_jpeg, normalize_orientation_jpeg, sbs_from_vr180_photo,
+                                  transform_jpeg)
 from .sharding import remap_sharded
 
 __all__ = [
@@ -74,4 +76,10 @@ __all__ = [
     "transcode_jpeg",
     "split_sbs_jpeg",
     "swap_sbs_jpeg",
+    # lossless join, rotation and flip of JPEG files in the DCT domain, from several files, on the device (join)
+    "compose_regions",
+    "transform_jpeg",
+    "join_sbs_jpeg",
+    "sbs_from_vr180_photo",
+    "normalize_orientation_jpeg",
 ]

@@ -29,6 +29,7 @@ SYMBOLS = [
     "v1c_jpeg_header_opt", "v1c_jpeg_encode_opt", "v1c_jpeg_encode_batch_opt",
     "v1c_jpeg_prog_info", "v1c_jpeg_prog_decode",
     "v1c_jpeg_transcode_bound", "v1c_jpeg_transcode_check", "v1c_jpeg_header_xc", "v1c_jpeg_transcode",
+    "v1c_jpeg_compose_bound", "v1c_jpeg_compose_check", "v1c_jpeg_header_xf", "v1c_jpeg_compose",
 ]
 
 
@@ -129,6 +130,15 @@ def lib() -> C.CDLL:
         L.v1c_jpeg_header_xc.argtypes = [C.c_char_p, C.c_uint64, i32, i32, i32, vp, C.c_uint32, vp, C.c_uint64]
         L.v1c_jpeg_header_xc.restype = i64
         L.v1c_jpeg_transcode.argtypes = [i32, vp, C.c_char_p, C.c_uint64, i32, vp, C.c_uint32, vp]
+    except AttributeError:  # (an older build behind V1C_LIB)
+        pass
+    try:
+        L.v1c_jpeg_compose_bound.argtypes = [C.c_char_p, C.c_uint64, i32, i32, i32]
+        L.v1c_jpeg_compose_bound.restype = C.c_uint64
+        L.v1c_jpeg_compose_check.argtypes = [i32, vp, i32, vp, vp]
+        L.v1c_jpeg_header_xf.argtypes = [C.c_char_p, C.c_uint64, i32, i32, i32, i32, vp, C.c_uint32, vp, C.c_uint64]
+        L.v1c_jpeg_header_xf.restype = i64
+        L.v1c_jpeg_compose.argtypes = [i32, vp, i32, vp, i32, vp, C.c_uint32, vp]
     except AttributeError:  # (an older build behind V1C_LIB)
         pass
     L.v1c_plan_run.argtypes = [vp, vp, C.POINTER(_abi.Unit), i32]

@@ -393,5 +393,48 @@ def xmp(
         LOG.info(f"Saved {written}")
 
 
+@app.command()
+def join(
+    in_paths: Annotated[List[Path], typer.Argument(help="LEFT RIGHT: the two eyes' .jpg / .jpeg files; or one Google VR180 photo")],
+    left_transform: Annotated[Optional[str], typer.Option("--left-transform", help="flip_h, flip_v, rot180, transpose, rot90 (clockwise), "
+                                                                                    "rot270 or transverse: applied to the left eye")] = None,
+    right_transform: Annotated[Optional[str], typer.Option("--right-transform", help="As --left-transform, for the right eye")] = None,
+    trim: Annotated[bool, typer.Option("--trim", help="Cut a partial last MCU column or row off where a mirror or the join needs whole "
+                                                      "MCUs, instead of refusing")] = False,
+    optimize: Annotated[bool, typer.Option("--optimize", help="Huffman tables built for the output on the GPU")] = False,
+    vr180: Annotated[bool, typer.Option("--vr180", help="Write the transformed eyes as a Google VR180 photo instead of side by side")] = False,
+    out_path: Annotated[Optional[Path], typer.Option("--out-path", help="Default: LEFT's name with .join (or .sbs for a VR180 photo) in "
+                                                                        "front of its suffix")] = None,
+) -> None:
+    """Join two per-eye JPEG files into one side-by-side file in the DCT domain on the GPU, each eye flipped or rotated on the way: no
+    pixel is decoded, no JPEG generation is lost.  With one argument, a Google VR180 photo, write its side-by-side file."""
+    from . import jpeg_compose_device as _xf, vr180_photo as _vp
+
+    from .jpeg_decode_device import CorruptJPEG
+
+    if len(in_paths) not in (1, 2):
+        raise typer.BadParameter("join takes LEFT RIGHT, or one VR180 photo")
+    try:
+        if len(in_paths) == 1:
+            left, right, _ = _vp.read_vr180_photo(in_paths[0].read_bytes())
+        else:
+            left, right = in_paths[0].read_bytes(), in_paths[1].read_bytes()
+        kw = dict(trim=trim, optimize=optimize)
+        if vr180:
+            eyes = [_xf.transform_jpeg(eye, t or "none", **kw) for eye, t in ((left, left_transform), (right, right_transform))]
+            (lh, lw, _, _), (rh, rw, _, _) = (_xf.probe_mcu(eye) for eye in eyes)
+            if lh != rh:
+                raise ValueError(f"the eyes end up {lh} and {rh} pixels high: a VR180 photo needs one height")
+            made = _vp.assemble_vr180_photo(eyes[0], eyes[1], lw + rw, lh)
+        else:
+            made = _xf.join_sbs_jpeg(left, right, left_transform=left_transform, right_transform=right_transform, **kw)
+    except (CorruptJPEG, NotImplementedError, ValueError) as e:  # nothing falls back: a join through pixels would lose a generation
+        raise typer.BadParameter(f"{in_paths[0]}: {e}") from e
+    p = in_paths[0]
+    written = out_path or p.with_suffix(f"{'.sbs' if len(in_paths) == 1 and not vr180 else '.join'}{p.suffix}")
+    written.write_bytes(made)
+    LOG.info(f"Saved {written}")
+
+
 def main(argv: Optional[Sequence[str]] = None) -> None:
     app(args=None if argv is None else list(argv), prog_name="vr180-convert")
