@@ -1,6 +1,7 @@
 """The lossless JPEG composer on the MI355X: every case of tests/jpgxf_cases.py through ``v1c_jpeg_compose`` against the restatement
 (jpgxf_ref.py), byte for byte, header and scan, at the default subsequence size and at 256 bits on a stream of its own; a damaged second
-source, out-of-range coefficients and the refusal under stream capture; the Python entries ``transform_jpeg``, ``join_sbs_jpeg``,
+source, out-of-range coefficients and the refusal under stream capture; one source with transform 0 against ``v1c_jpeg_transcode``,
+field by field; the Python entries ``transform_jpeg``, ``join_sbs_jpeg``,
 ``sbs_from_vr180_photo`` and ``normalize_orientation_jpeg``; and ``join`` on the command line, behind ``xmp --device`` and with
 ``--vr180``.  tests/test_jpegxf_host.py runs the same cases through the host build of the arithmetic, which tells a wrong rule from
 wrong kernel plumbing."""
@@ -124,6 +125,42 @@ def test_refused_under_stream_capture(lib):
     assert (buf == 0xA5).all() and all(r.rounds == 0 for r in reps)
     rc, _, files, _ = compose(lib, *CASES[name], 0)
     assert rc == 0 and files == list(K.reference(name))
+
+
+@pytest.mark.parametrize("S", [0, 256])
+@pytest.mark.parametrize("name, optimize_first", [("swap_2x2_420", False), ("source_dri2_422", False), ("noise_q100_420_split", True)])
+def test_one_source_untransformed_is_the_transcoder_s_call(lib, name, optimize_first, S):
+    """``v1c_jpeg_transcode`` and ``v1c_jpeg_compose`` of one source with transform 0 are one host chain: the same return code, the same
+    scans, sizes and tables, the same report -- over two regions, an MCU of two luma blocks with restart markers in the source, and a head
+    with an optimising and an Annex K output"""
+    import jpgxc_cases as XK
+    from test_jpegxc_host import _xc_outputs
+
+    data, outputs = XK.cases()[name]
+    if optimize_first:
+        outputs = [dict(outputs[0], optimize=True)] + list(outputs[1:])
+        assert len(outputs) == 2
+    st = torch.cuda.current_stream().cuda_stream
+
+    def run(outs, call):
+        bounds = [int(lib.v1c_jpeg_transcode_bound(data, len(data), o.width, o.height, o.restart_mcus)) for o in outs]
+        assert all(bounds)
+        buf, at = np.full(sum(bounds), 0xA5, np.uint8), 0
+        for o, b in zip(outs, bounds):
+            o.out_host, o.capacity = buf.ctypes.data + at, b
+            at += b
+        rep = Report()
+        rc = call(outs, rep)
+        return rc, [(int(o.size), int(o.dht_size), bytes(o.dht[:o.dht_size])) for o in outs], buf.tobytes(), (rep.segments, rep.subsequences, rep.rounds)
+
+    xc_outs, keep_xc = _xc_outputs(outputs, X.Source(data))
+    one = run(xc_outs, lambda outs, rep: lib.v1c_jpeg_transcode(0, st, data, len(data), len(outs), outs, S, C.byref(rep)))
+    srcs, xf_outs, keep_xf = _xf_call([data], [dict(o, regions=[(0, 0) + tuple(r) for r in o["regions"]]) for o in outputs])
+    two = run(xf_outs, lambda outs, rep: lib.v1c_jpeg_compose(0, st, 1, srcs, len(outs), outs, S, C.byref(rep)))
+    assert one[0] == two[0] == 0, lib.v1c_last_error()
+    assert one == two
+    assert all(size > 0 for size, _, _ in one[1]) and [bool(n) for _, n, _ in one[1]] == [bool(o.get("optimize")) for o in outputs]
+    assert one[3][2] >= 1 and one[3][1] >= one[3][0] >= 1
 
 
 # ---- the Python entries ----------------------------------------------------------------------------------------------------------------

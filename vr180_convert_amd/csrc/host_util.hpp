@@ -1,6 +1,6 @@
-// host_util.hpp -- what the host sides of the C ABI's entry points (plan.hip, feat.hip, png.hip, jpeg.hip, jpegdec.hip) share: the error
-// message, the device of a call, its stream-ordered workspace and the alignment of the buffers in it, and whether its stream is being
-// captured.  Host code only.
+// host_util.hpp -- what the host sides of the C ABI's entry points (plan.hip, feat.hip, png.hip, jpeg.hip, jpegdec.hip, jpegxc.hip,
+// jpegxf.hip) share: the error message, the device of a call and the ordinals the decoding entries take, its stream-ordered workspace
+// and the alignment of the buffers in it, and whether its stream is being captured.  Host code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +11,8 @@
 namespace v1c {
 
 int set_error(int code, const std::string& msg);  // plan.hip: the message v1c_last_error returns
+
+constexpr int kMaxDevices = 64;  // device ordinals the JPEG decoding entries take: one staging buffer each (jpegdec.hip)
 
 // the device of one call; the caller's comes back on every way out
 struct DeviceGuard {

@@ -1,6 +1,7 @@
 // jpeg.hip -- host side of the JPEG entry points of the C ABI (v1c_jpeg_*, include/vr180_remap.h): argument checks, the tables, the
 // chain of kernels, and the two copies to the host (the size, then the scan).  The optimising entries (v1c_jpeg_*_opt) run the same
-// chunks with the tables of jpeg_opt_core.hpp built on the device between two stages; their records come with the sizes.
+// chunks with the tables of jpeg_opt_core.hpp built on the device between two stages; their records come with the sizes.  Where a
+// chunk's pieces lie in its workspace, and its end from the sizes on, is jpeg_chunk.hpp's, which the lossless entries share.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,6 +12,7 @@
 #include "../../include/vr180_remap.h"
 #include "host_util.hpp"
 #include "jpeg_batch.hpp"
+#include "jpeg_chunk.hpp"
 #include "jpeg_host.hpp"
 #include "jpeg_launch.hpp"
 #include "jpeg_opt_kernels.hpp"
@@ -43,49 +45,13 @@ std::string image_error(const void* img, int h, int w, int64_t pitch, int cn, in
     return std::string();
 }
 
-// The workspace of a call on ws: the `head` bytes the call lays out itself, and behind them the encoder's buffers for `t` entries back to
-// back, each aligned to 256 bytes.
-struct BufferSet {
-    Buffers buf;
-    size_t raw_bytes;  // of buf.raw, to be zeroed
-    size_t bytes;      // of the workspace, head included
-};
-
-hipError_t allocate_buffers(Workspace& ws, size_t head, const Totals& t, BufferSet& s)
-{
-    s.raw_bytes = align256(t.pieces * kPiece + 16);
-    const size_t o_coef = head, o_bits = o_coef + align256(t.nblocks * 128), o_bitoff = o_bits + align256(t.nblocks * 4);
-    const size_t o_ibytes = o_bitoff + align256((t.nblocks + 1) * 8), o_ioff = o_ibytes + align256(t.nint * 4);
-    const size_t o_raw = o_ioff + align256((t.nint + 1) * 8), o_ffcnt = o_raw + s.raw_bytes, o_ffoff = o_ffcnt + align256(t.pieces * 4);
-    const size_t o_sums = o_ffoff + align256((t.pieces + 1) * 8), o_out = o_sums + align256(sums_of(t, kScanChunk) * 8);
-    s.bytes = o_out + align256(t.out_bytes + 8);
-    const hipError_t e = hipMallocAsync((void**)&ws.p, s.bytes, ws.st);
-    if (e != hipSuccess)
-        return e;
-    uint8_t* base = ws.p;
-    s.buf.coef = (int16_t*)(base + o_coef);
-    s.buf.bits = (uint32_t*)(base + o_bits);
-    s.buf.bitoff = (uint64_t*)(base + o_bitoff);
-    s.buf.ibytes = (uint32_t*)(base + o_ibytes);
-    s.buf.ioff = (uint64_t*)(base + o_ioff);
-    s.buf.raw = (uint32_t*)(base + o_raw);
-    s.buf.ffcnt = (uint32_t*)(base + o_ffcnt);
-    s.buf.ffoff = (uint64_t*)(base + o_ffoff);
-    s.buf.sums = (uint64_t*)(base + o_sums);
-    s.buf.out = base + o_out;
-    return hipSuccess;
-}
-
-// One image of a list, of either entry: the caller's arguments, where its results go, and whether it builds tables of its own
+// One image of a list, of either entry: the caller's arguments, whether it builds tables of its own, and where its results go
 struct Item {
     const void* img;
     int64_t pitch;
     int quality;
-    uint8_t* out_host;
-    uint64_t* size;
     bool optimize;
-    uint8_t* dht;        // optimising images: V1C_JPEG_DHT_MAX bytes for the DHT segment's body
-    uint32_t* dht_size;
+    Result to;
 };
 
 // One chunk of a batch: images [lo, hi) in one allocation, one upload and one chain of kernels; then all sizes (and the records of the
@@ -116,78 +82,39 @@ hipError_t encode_chunk(hipStream_t st, const std::vector<Item>& images, const s
         quality.push_back(images[lo + f].quality);
     }
     const size_t nslots = slots.size();
-    const size_t o_im = 0, o_first = o_im + align256((size_t)n * sizeof(Image)), o_tabs = o_first + align256((size_t)kWorkLists * (n + 1) * 4);
-    const size_t o_slotof = o_tabs + align256(quality.size() * sizeof(Tables));
-    const size_t o_slots = o_slotof + (nslots ? align256((size_t)n * 4) : 0), o_sizes = o_slots + align256(nslots * sizeof(OptSlot));
-    // read back in one copy: the sizes, then the records; zeroed with them: the histograms
-    const size_t o_rec = o_sizes + align256((size_t)n * 8), o_hist = o_rec + align256(nslots * sizeof(DhtRecord));
-    const size_t head = o_hist + align256(nslots * sizeof(Hist));
-    const size_t back_bytes = nslots ? o_rec + nslots * sizeof(DhtRecord) - o_sizes : (size_t)n * 8;
-    std::vector<uint8_t> up(o_sizes, 0);  // (pageable: alive until the first synchronisation below, on every way out)
-    Image* im = (Image*)(up.data() + o_im);
-    uint32_t* first = (uint32_t*)(up.data() + o_first);
+    const HeadLayout h = head_layout(n, quality.size(), nslots, false);
+    std::vector<uint8_t> up(h.o_sizes, 0);  // (pageable: alive until the first synchronisation of finish_chunk, on every way out)
+    Image* im = (Image*)(up.data() + h.o_im);
+    uint32_t* first = (uint32_t*)(up.data() + h.o_first);
     for (uint32_t f = 0; f < n; f++) {
         const Item& v = images[lo + f];
         im[f].img = (const uint8_t*)v.img, im[f].pitch = v.pitch, im[f].g = geoms[lo + f], im[f].tab = tab_of[f];
     }
     const Totals t = place_regions(im, n, first);
     for (size_t k = 0; k < quality.size(); k++)
-        make_tables(quality[k], ((Tables*)(up.data() + o_tabs))[k]);
-    if (nslots) {
-        std::memcpy(up.data() + o_slotof, slot_of.data(), (size_t)n * 4);
-        std::memcpy(up.data() + o_slots, slots.data(), nslots * sizeof(OptSlot));
-    }
+        make_tables(quality[k], ((Tables*)(up.data() + h.o_tabs))[k]);
+    stage_slots(up.data(), h, slot_of, slots);
 
     Workspace ws(st);
     what = "hipMallocAsync";
-    BufferSet bs;
-    hipError_t e = allocate_buffers(ws, head, t, bs);
+    const StageLayout sl = stage_layout(h.bytes, t);
+    hipError_t e = hipMallocAsync((void**)&ws.p, sl.bytes, st);
     if (e != hipSuccess)
         return e;
-    Batch b{};
-    b.im = (const Image*)(ws.p + o_im), b.first = (const uint32_t*)(ws.p + o_first), b.tabs = (const Tables*)(ws.p + o_tabs);
-    b.n = n, b.t = t;
-    b.sizes = (uint64_t*)(ws.p + o_sizes);
-    b.buf = bs.buf;
-    OptBatch o{};
-    o.slot_of = (const int32_t*)(ws.p + o_slotof), o.slots = (const OptSlot*)(ws.p + o_slots), o.nslots = (uint32_t)nslots;
-    o.hist = (Hist*)(ws.p + o_hist), o.rec = (DhtRecord*)(ws.p + o_rec), o.tabs = (Tables*)(ws.p + o_tabs);
+    Batch b;
+    OptBatch o;
+    chunk_args(h, ws.p, n, nslots, t, sl.at(ws.p), b, o);
 
-    what = "kernels";
-    std::vector<uint8_t> back(back_bytes, 0);
-    e = hipMemcpyAsync(ws.p, up.data(), o_sizes, hipMemcpyHostToDevice, st);
+    e = hipMemcpyAsync(ws.p, up.data(), h.o_sizes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
-        e = hipMemsetAsync(b.buf.raw, 0, bs.raw_bytes, st);
+        e = hipMemsetAsync(b.buf.raw, 0, sl.raw_bytes, st);
     if (e == hipSuccess)
-        e = hipMemsetAsync(b.sizes, 0, nslots ? head - o_sizes : (size_t)n * 8, st);
+        e = hipMemsetAsync(b.sizes, 0, h.zero_bytes, st);
     if (e == hipSuccess)
         e = nslots ? launch_encode_batch_opt(b, o, first, st) : launch_encode_batch(b, first, st);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(back.data(), b.sizes, back_bytes, hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);  // 1: the sizes and the records
-    if (e == hipSuccess)
-        e = es;
-    if (e != hipSuccess)
-        return e;
-    const uint64_t* sizes = (const uint64_t*)back.data();
-    what = "internal size estimate exceeded";
-    for (uint32_t f = 0; f < n; f++)
-        if (sizes[f] == 0 || sizes[f] > scan_bound(im[f].g))
-            return hipErrorUnknown;
-    what = "copy";
-    for (uint32_t f = 0; f < n && e == hipSuccess; f++)
-        e = hipMemcpyAsync(images[lo + f].out_host, b.buf.out + im[f].out0, sizes[f], hipMemcpyDeviceToHost, st);
-    const hipError_t ec = hipStreamSynchronize(st);  // 2: the scans
-    if (e == hipSuccess)
-        e = ec;
-    if (e != hipSuccess)
-        return e;
-    for (uint32_t f = 0; f < n; f++) {
-        *images[lo + f].size = sizes[f];
-        if (slot_of[f] >= 0)
-            *images[lo + f].dht_size = dht_body(((const DhtRecord*)(back.data() + (o_rec - o_sizes)))[slot_of[f]], images[lo + f].dht);
-    }
-    return hipSuccess;
+    const char* const steps[] = {"", "kernels", "internal size estimate exceeded", "copy"};
+    what = steps[finish_chunk(b, h, im, slot_of, [&](uint32_t f) { return images[lo + f].to; }, st, e)];
+    return e;
 }
 
 // a checked list in chunks under the budget; `name`: the entry, for the messages
@@ -202,7 +129,7 @@ int encode_list(int device, void* stream, const std::vector<Item>& items, const 
         return set_error(V1C_E_UNSUPPORTED, name + ": the host reads the sizes between the kernels and the copies, so the call cannot be captured into a graph");
     std::vector<uint64_t> bytes, groups;
     for (size_t i = 0; i < items.size(); i++) {
-        *items[i].size = 0;
+        *items[i].to.size = 0;
         bytes.push_back(workspace_of(geoms[i]) + (items[i].optimize ? sizeof(Tables) + sizeof(Hist) + sizeof(DhtRecord) + sizeof(OptSlot) + 4 + 1280 : 0));
         groups.push_back(most_groups(geoms[i]));
     }
@@ -222,20 +149,7 @@ int encode_list(int device, void* stream, const std::vector<Item>& items, const 
 // the segments in front of the scan with the DHT body of an optimising encode in place of the Annex K tables'
 bool header_with_dht(const Geom& g, int quality, const uint8_t* dht, uint32_t dht_size, std::vector<uint8_t>& out)
 {
-    // the body must be whole tables: the two of one component, or the four of three, in the segment's order
-    const uint8_t ids[4] = {0x00, 0x10, 0x01, 0x11};
-    uint32_t at = 0, tables = 0;
-    while (at < dht_size && tables < 4) {
-        if (dht[at] != ids[tables] || at + 17 > dht_size)
-            return false;
-        uint32_t nsym = 0;
-        for (int i = 0; i < 16; i++)
-            nsym += dht[at + 1 + i];
-        if (nsym < 1 || nsym > 256)
-            return false;
-        at += 17 + nsym, tables++;
-    }
-    if (at != dht_size || tables != (g.nc == 1 ? 2u : 4u))
+    if (!whole_tables(dht, dht_size, g.nc))
         return false;
     out = file_header(g, quality, dht, dht_size);
     return true;
@@ -278,9 +192,9 @@ extern "C" int v1c_jpeg_encode(int device, void* stream, const void* img, int h,
     hipStream_t st = (hipStream_t)stream;
     const Totals t{g.nblocks, g.nint, pieces_of(g), cap};
     const size_t o_tab = 0, o_total = o_tab + align256(sizeof(Tables)), head = o_total + 256;
+    const StageLayout sl = stage_layout(head, t);
     Workspace ws(st);
-    BufferSet bs;
-    hipError_t e = allocate_buffers(ws, head, t, bs);
+    hipError_t e = hipMallocAsync((void**)&ws.p, sl.bytes, st);
     if (e != hipSuccess)
         return set_error(V1C_E_HIP, std::string("v1c_jpeg_encode: hipMallocAsync: ") + hipGetErrorString(e));
     Args a{};
@@ -289,14 +203,14 @@ extern "C" int v1c_jpeg_encode(int device, void* stream, const void* img, int h,
     a.g = g;
     a.tab = (const Tables*)(ws.p + o_tab);
     a.total = (uint64_t*)(ws.p + o_total);
-    a.buf = bs.buf;
+    a.buf = sl.at(ws.p);
 
     Tables tab;  // (pageable: alive until the first synchronisation below, on every way out)
     make_tables(quality, tab);
     uint64_t total = 0;
     e = hipMemcpyAsync(ws.p + o_tab, &tab, sizeof(tab), hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
-        e = hipMemsetAsync(a.buf.raw, 0, bs.raw_bytes, st);
+        e = hipMemsetAsync(a.buf.raw, 0, sl.raw_bytes, st);
     if (e == hipSuccess)
         e = hipMemsetAsync(a.total, 0, 8, st);
     if (e == hipSuccess)
@@ -339,7 +253,7 @@ extern "C" int v1c_jpeg_encode_batch(int device, void* stream, int n, v1c_jpeg_i
     }
     std::vector<Item> items;
     for (int i = 0; i < n; i++)
-        items.push_back(Item{images[i].img, images[i].pitch, images[i].quality, images[i].out_host, &images[i].size, false, nullptr, nullptr});
+        items.push_back(Item{images[i].img, images[i].pitch, images[i].quality, false, {images[i].out_host, &images[i].size, nullptr, nullptr}});
     return encode_list(device, stream, items, geoms, workspace_budget, chunks_out, "v1c_jpeg_encode_batch");
 }
 
@@ -369,7 +283,7 @@ extern "C" int v1c_jpeg_encode_opt(int device, void* stream, const void* img, in
     if (!bad.empty())
         return set_error(V1C_E_INVALID, "v1c_jpeg_encode_opt: " + bad);
     *dht_size_out = 0;
-    const std::vector<Item> items = {Item{img, pitch, quality, out_host, size_out, true, dht_out, dht_size_out}};
+    const std::vector<Item> items = {Item{img, pitch, quality, true, {out_host, size_out, dht_out, dht_size_out}}};
     return encode_list(device, stream, items, geoms, 0, nullptr, "v1c_jpeg_encode_opt");
 }
 
@@ -391,7 +305,7 @@ extern "C" int v1c_jpeg_encode_batch_opt(int device, void* stream, int n, v1c_jp
         if (!bad.empty())
             return set_error(V1C_E_INVALID, "v1c_jpeg_encode_batch_opt: image " + std::to_string(i) + ": " + bad);
         v.dht_size = 0;
-        items.push_back(Item{v.img, v.pitch, v.quality, v.out_host, &v.size, v.optimize != 0, v.dht, &v.dht_size});
+        items.push_back(Item{v.img, v.pitch, v.quality, v.optimize != 0, {v.out_host, &v.size, v.dht, &v.dht_size}});
     }
     return encode_list(device, stream, items, geoms, workspace_budget, chunks_out, "v1c_jpeg_encode_batch_opt");
 }

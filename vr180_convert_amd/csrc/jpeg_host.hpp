@@ -1,5 +1,6 @@
 // jpeg_host.hpp -- host side of the device JPEG encoder: the Annex K tables of ISO/IEC 10918-1, the quantisation tables of a quality,
-// the code tables the kernels read, and the header segments of the file.  Shared by jpeg.hip and tests/host_jpeg/jpeg_emul.hip.
+// the code tables the kernels read, the header segments of the file, and the rule of a DHT body that a caller hands back.  Shared by
+// jpeg.hip, the lossless entries and tests/host_jpeg/jpeg_emul.hip.
 #pragma once
 
 #include <cstring>
@@ -81,6 +82,24 @@ inline void make_tables(int quality, Tables& t)
     code_table(kDcChroma, t.dc[1], 16);
     code_table(kAcLuma, t.ac[0], 256);
     code_table(kAcChroma, t.ac[1], 256);
+}
+
+// whether a DHT body is whole tables in the segment's order: the two of one component, or the four of three
+inline bool whole_tables(const uint8_t* dht, uint32_t dht_size, uint32_t nc)
+{
+    const uint8_t ids[4] = {0x00, 0x10, 0x01, 0x11};
+    uint32_t at = 0, tables = 0;
+    while (at < dht_size && tables < 4) {
+        if (dht[at] != ids[tables] || at + 17 > dht_size)
+            return false;
+        uint32_t nsym = 0;
+        for (int i = 0; i < 16; i++)
+            nsym += dht[at + 1 + i];
+        if (nsym < 1 || nsym > 256)
+            return false;
+        at += 17 + nsym, tables++;
+    }
+    return at == dht_size && tables == (nc == 1 ? 2u : 4u);
 }
 
 inline void put_segment(std::vector<uint8_t>& out, int marker, const std::vector<uint8_t>& body)

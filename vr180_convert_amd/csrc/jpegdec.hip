@@ -1,6 +1,6 @@
 // jpegdec.hip -- host side of the JPEG decoding entry points of the C ABI (v1c_jpeg_decode*, include/vr180_remap.h): the parse, the
-// upload from the page-locked staging buffer, the chain of kernels and the rounds of the synchronisation, whose flag the host reads;
-// and the same for a batch of files in shared launches and rounds (v1c_jpeg_decode_batch); and for a progressive
+// upload from the page-locked staging buffer, the chain of kernels and the rounds of the synchronisation, whose flag the host reads
+// (jpegdec_launch.hpp: decode_to_coef, the step the lossless entries share); and the same for a batch of files in shared launches and rounds (v1c_jpeg_decode_batch); and for a progressive
 // file scan by scan (v1c_jpeg_prog_decode).
 #include <hip/hip_runtime.h>
 
@@ -26,7 +26,6 @@ namespace {
 // the word that comes back.  Each has a lock of its own, held by a call from filling the buffer to its last synchronisation, so the
 // buffer is never rewritten under a copy in flight: decodes on ONE device take turns (whatever their streams), decodes on different
 // devices do not meet.
-constexpr int kMaxDevices = 64;
 struct Staging {
     std::mutex mu;
     uint8_t* p = nullptr;
@@ -55,14 +54,6 @@ int parse_error(ParseResult r, const Parsed& p, std::string& why)
     why = p.why + " (byte " + std::to_string(p.error_pos) + ")";
     return r == kUnsupported ? V1C_E_UNSUPPORTED : V1C_E_CORRUPT;
 }
-
-// The bits of a subsequence that subseq_bits asks for, or 0 where it breaks the rule.
-uint32_t subseq_of(uint32_t subseq_bits)
-{
-    const uint32_t S = subseq_bits ? subseq_bits : kDefaultSubseqBits;
-    return S % 32 || S < 256 || S > (1u << 24) ? 0 : S;
-}
-const char* const kSubseqRule = "subseq_bits must be a multiple of 32 from 256 to 2^24, or 0";
 
 // Whether a file can be decoded into its destination, for the single call and for every file of a batch: V1C_OK and the parse in ps, or
 // the code and what is wrong.  Where the parse refused the file, ps.error_pos has the byte.
@@ -133,7 +124,7 @@ extern "C" int v1c_jpeg_decode(int device, void* stream, const uint8_t* file, ui
         report->segments = nseg, report->subsequences = nsub;
     // the upload (tables, segment offsets, first subsequences, the scan) and behind it what the kernels make
     const Layout l = layout_of(ps, nsub);
-    const size_t up_bytes = l.up_bytes, u_bytes = l.u_bytes, coef_bytes = l.coef_bytes;
+    const size_t up_bytes = l.up_bytes;
 
     Staging& sg = g_staging[device];
     std::lock_guard<std::mutex> lock(sg.mu);
@@ -150,35 +141,10 @@ extern "C" int v1c_jpeg_decode(int device, void* stream, const uint8_t* file, ui
         return set_error(V1C_E_HIP, std::string("v1c_jpeg_decode: hipMallocAsync: ") + hipGetErrorString(e));
     const Args a = args_of(ps, l, nsub, S, ws.p, ws.p + up_bytes, (uint32_t*)(ws.p + up_bytes + l.o_flags), out, pitch, out_cn);
 
-    e = hipMemcpyAsync(ws.p, stage, up_bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(a.flags, 0, 8, st);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(a.flags + 2, 0xff, 4, st);  // kNoError
-    if (e == hipSuccess)
-        e = hipMemsetAsync(a.u, 0, u_bytes, st);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(a.coef, 0, coef_bytes, st);
-    if (e == hipSuccess)
-        e = launch_unstuff(a, st);
-    if (e == hipSuccess)
-        e = launch_sync_init(a, st);
-    // the rounds: at most nsub + 1, since round r fixes the first r entry states of every segment for good
     uint32_t r = 0;
-    while (e == hipSuccess) {
-        r++;
-        e = launch_sync_round(a, r, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync((void*)back, a.flags + (r & 1u), 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(st);
-        if (e != hipSuccess || back[0] == 0 || r > nsub)
-            break;
-    }
+    e = decode_to_coef(a, l, stage, nsub, st, back, &r);
     if (report)
         report->rounds = r;
-    if (e == hipSuccess)
-        e = launch_write(a, r, st);
     if (e == hipSuccess)
         e = hipMemcpyAsync((void*)back, a.flags + 2, 4, hipMemcpyDeviceToHost, st);
     const hipError_t es = hipStreamSynchronize(st);  // (also on an error above: nothing of this call is in flight when the lock goes)

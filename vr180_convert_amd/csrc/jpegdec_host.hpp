@@ -1,6 +1,7 @@
 // jpegdec_host.hpp -- host side of the device JPEG decoder: the marker parser, the construction of the decoder's tables, the geometry
 // and the walk over the scan's 0xFF bytes that finds the scan's end and its RSTm markers.  Everything a file can be refused for without
-// decoding it is found here, before the device is touched (v1c_jpeg_decode_info is this parse alone).  Shared by jpegdec.hip and the
+// decoding it is found here, before the device is touched (v1c_jpeg_decode_info is this parse alone), and the rule of subseq_bits of
+// every entry that decodes (subseq_of).  Shared by jpegdec.hip, the lossless entries (jpegx_chain.hpp) and the
 // host harness (tests/host_jpegdec/jpegdec_emul.hip); tests/jpgdec_ref.py restates it.
 #pragma once
 
@@ -229,6 +230,14 @@ inline ParseResult parse(const uint8_t* d, uint64_t n, Parsed& out)
             return fail(out, kCorrupt, pos, "an empty segment");
     return kParsed;
 }
+
+// The bits of a subsequence that an entry's subseq_bits asks for, or 0 where it breaks the rule.
+inline uint32_t subseq_of(uint32_t subseq_bits)
+{
+    const uint32_t S = subseq_bits ? subseq_bits : kDefaultSubseqBits;
+    return S % 32 || S < 256 || S > (1u << 24) ? 0 : S;
+}
+constexpr const char* kSubseqRule = "subseq_bits must be a multiple of 32 from 256 to 2^24, or 0";
 
 // the first subsequence of every segment (nseg + 1 entries): a segment's bits are tiled by S, and no subsequence spans two segments
 inline std::vector<uint32_t> sub_first(const Parsed& p, uint32_t S)

@@ -1,4 +1,5 @@
-// jpegdec_launch.hpp -- launchers of the JPEG decoder's kernels (kernels_jpegdec.hip), called by the C ABI in jpegdec.hip.
+// jpegdec_launch.hpp -- launchers of the JPEG decoder's kernels (kernels_jpegdec.hip), called by the C ABI in jpegdec.hip, and the
+// host's step from one file's upload to its coefficients (decode_to_coef), which the lossless entries (jpegx_chain.hpp) run too.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -130,6 +131,43 @@ hipError_t launch_sync_round(const Args& a, uint32_t r, hipStream_t st);
 hipError_t launch_write(const Args& a, uint32_t r, hipStream_t st);
 // DC scan, inverse DCT into the planes, upsampling and colour conversion into a.out
 hipError_t launch_pixels(const Args& a, hipStream_t st);
+
+// One file from its staged upload to its coefficients, for every entry that decodes one file at a time (v1c_jpeg_decode, and the
+// lossless entries source by source): the upload from `stage` (host memory, l.up_bytes; a's upload lies at a.tab), the zeroing of the
+// flags, the error word, a.u and a.coef, the unstuffing, and the rounds -- at most nsub + 1, since round r fixes the first r entry
+// states of every segment for good -- with the last pass behind them.  The host reads a flag between the rounds: *more (host memory)
+// receives it, and the stream is SYNCHRONISED once per round; the last pass is queued, not waited for.  `stage` and `more` must stay
+// alive until the caller's next synchronisation.  Returns the first error, and the rounds in *rounds whatever happened.
+inline hipError_t decode_to_coef(const Args& a, const Layout& l, const uint8_t* stage, uint32_t nsub, hipStream_t st, volatile uint32_t* more,
+                                 uint32_t* rounds)
+{
+    hipError_t e = hipMemcpyAsync((uint8_t*)a.tab - l.o_tab, stage, l.up_bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(a.flags, 0, 8, st);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(a.flags + 2, 0xff, 4, st);  // kNoError
+    if (e == hipSuccess)
+        e = hipMemsetAsync(a.u, 0, l.u_bytes, st);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(a.coef, 0, l.coef_bytes, st);
+    if (e == hipSuccess)
+        e = launch_unstuff(a, st);
+    if (e == hipSuccess)
+        e = launch_sync_init(a, st);
+    uint32_t r = 0;
+    while (e == hipSuccess) {
+        r++;
+        e = launch_sync_round(a, r, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync((void*)more, a.flags + (r & 1u), 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(st);
+        if (e != hipSuccess || *more == 0 || r > nsub)
+            break;
+    }
+    *rounds = r;
+    return e == hipSuccess ? launch_write(a, r, st) : e;
+}
 
 // ---- a batch: a chunk of n files in shared launches (kernels_jpegdec_batch.hip) --------------------------------
 struct Batch {

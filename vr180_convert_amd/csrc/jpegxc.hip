@@ -1,8 +1,7 @@
 // jpegxc.hip -- host side of the lossless JPEG transcoder's entry points of the C ABI (v1c_jpeg_transcode*, v1c_jpeg_header_xc,
-// include/vr180_remap.h): the parse and the rules of the outputs, all before the device is touched; then the decoder's chain up to its
-// DC scan with the rounds the host reads a flag between, the gather of every output, and the batch encoder's chain from a filled
-// coefficient store on, with its two synchronisations.  The outputs of a call are the images of one encoder chunk.  INTEGRATION.md
-// section 9 has the contract, DESIGN.md section 19 the design.
+// include/vr180_remap.h): the parse and the rules of the outputs, all before the device is touched; then the lossless entries' one
+// chain (jpegx_chain.hpp) over the one source, with this entry's gather.  The outputs of a call are the images of one encoder chunk.
+// INTEGRATION.md section 9 has the contract, DESIGN.md section 19 the design.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,16 +11,15 @@
 
 #include "../../include/vr180_remap.h"
 #include "host_util.hpp"
-#include "jpeg_host.hpp"
+#include "jpegx_chain.hpp"
 #include "jpegxc_host.hpp"
 #include "jpegxc_launch.hpp"
 
 using namespace v1c;
 using namespace v1c::jpegxc;
+using jpegx::file_error;
 
 namespace {
-
-constexpr int kMaxDevices = 64;
 
 // what the host-only checks of a call give: the parse, and every output's geometry and regions
 struct Checked {
@@ -29,19 +27,6 @@ struct Checked {
     std::vector<jpeg::Geom> geoms;
     std::vector<RegionList> lists;
 };
-
-// the parse and the file's scope: V1C_OK, or the code and why
-int file_error(const uint8_t* file, uint64_t size, jpegdec::Parsed& ps, std::string& why)
-{
-    if (!file)
-        return why = "NULL pointer", V1C_E_INVALID;
-    const jpegdec::ParseResult pr = jpegdec::parse(file, size, ps);
-    if (pr != jpegdec::kParsed) {
-        why = ps.why + " (byte " + std::to_string(ps.error_pos) + ")";
-        return pr == jpegdec::kUnsupported ? V1C_E_UNSUPPORTED : V1C_E_CORRUPT;
-    }
-    return source_error(ps, why);
-}
 
 // every check that needs no device; buffers: whether out_host and capacity count
 int call_error(const uint8_t* file, uint64_t size, int n, const v1c_jpeg_xc_output* outputs, bool buffers, Checked& c, std::string& why)
@@ -63,20 +48,6 @@ int call_error(const uint8_t* file, uint64_t size, int n, const v1c_jpeg_xc_outp
                    V1C_E_INVALID;
     }
     return V1C_OK;
-}
-
-// The tables an output's stages read: the Annex K codes (an optimising output's are overwritten on the device); the quantiser half
-// is the file's, which no stage behind the transform reads.
-void make_tables(const jpegdec::Parsed& ps, jpeg::Tables& t)
-{
-    for (int i = 0; i < 64; i++) {
-        t.q[0][i] = ps.tab.q[ps.g.tq[0]][i];
-        t.q[1][i] = ps.tab.q[ps.g.tq[ps.g.nc == 3 ? 1 : 0]][i];
-    }
-    jpeg::code_table(jpeg::kDcLuma, t.dc[0], 16);
-    jpeg::code_table(jpeg::kDcChroma, t.dc[1], 16);
-    jpeg::code_table(jpeg::kAcLuma, t.ac[0], 256);
-    jpeg::code_table(jpeg::kAcChroma, t.ac[1], 256);
 }
 
 }  // namespace
@@ -112,7 +83,7 @@ extern "C" int64_t v1c_jpeg_header_xc(const uint8_t* file, uint64_t size, int wi
     jpeg::Geom g;
     if (!out || !out_geom(ps.g, width, height, restart_mcus, g))
         return set_error(V1C_E_INVALID, "v1c_jpeg_header_xc: NULL pointer, or sizes or restart_mcus out of range");
-    if (dht && (dht_size > V1C_JPEG_DHT_MAX || !whole_tables(dht, dht_size, ps.g.nc)))
+    if (dht && (dht_size > V1C_JPEG_DHT_MAX || !jpeg::whole_tables(dht, dht_size, ps.g.nc)))
         return set_error(V1C_E_INVALID, "v1c_jpeg_header_xc: dht is not the tables of an optimising transcode of such a file");
     const std::vector<uint8_t> head = xc_header(ps, g, restart_mcus, dht, dht_size);
     if (capacity < head.size())
@@ -124,13 +95,11 @@ extern "C" int64_t v1c_jpeg_header_xc(const uint8_t* file, uint64_t size, int wi
 extern "C" int v1c_jpeg_transcode(int device, void* stream, const uint8_t* file, uint64_t size, int n, v1c_jpeg_xc_output* outputs,
                                   uint32_t subseq_bits, v1c_jpeg_decode_report* report)
 {
-    using jpeg::Image;
-    using jpeg::Tables;
     if (report)
         std::memset(report, 0, sizeof(*report));
-    const uint32_t S = subseq_bits ? subseq_bits : jpegdec::kDefaultSubseqBits;
-    if (S % 32 || S < 256 || S > (1u << 24))
-        return set_error(V1C_E_INVALID, "v1c_jpeg_transcode: subseq_bits must be a multiple of 32 from 256 to 2^24, or 0");
+    const uint32_t S = jpegdec::subseq_of(subseq_bits);
+    if (!S)
+        return set_error(V1C_E_INVALID, std::string("v1c_jpeg_transcode: ") + jpegdec::kSubseqRule);
     Checked c;
     std::string why;
     const int bad = call_error(file, size, n, outputs, true, c, why);
@@ -139,181 +108,15 @@ extern "C" int v1c_jpeg_transcode(int device, void* stream, const uint8_t* file,
             report->error_pos = c.ps.error_pos;
         return set_error(bad, "v1c_jpeg_transcode: " + why);
     }
-    const jpegdec::Parsed& ps = c.ps;
-    const jpegdec::Geom& sg = ps.g;
-
-    if (device < 0 || device >= kMaxDevices)
-        return set_error(V1C_E_NODEVICE, "v1c_jpeg_transcode: no such device");
-    DeviceGuard dg(device);
-    if (!dg.ok)
-        return set_error(V1C_E_NODEVICE, "hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    if (stream_is_capturing(st))
-        return set_error(V1C_E_UNSUPPORTED, "v1c_jpeg_transcode: the host reads a flag between the rounds and the sizes between the kernels and the "
-                                            "copies, so the call cannot be captured into a graph");
+    std::vector<jpegx::Output> out;
     for (int i = 0; i < n; i++)
-        outputs[i].size = 0, outputs[i].dht_size = 0;
-
-    // the decoder's part of the workspace: its upload, and its work up to the planes, which no pixel stage fills here
-    const std::vector<uint32_t> subfirst = jpegdec::sub_first(ps, S);
-    const uint32_t nsub = subfirst.back();
-    if (report)
-        report->segments = sg.nseg, report->subsequences = nsub;
-    const jpegdec::Layout l = jpegdec::layout_of(ps, nsub);
-    const size_t dec_bytes = l.up_bytes + l.o_p0;
-
-    // the encoder's part, as a chunk of v1c_jpeg_encode_batch_opt lays it out: the head -- descriptors, work lists, one Tables per output,
-    // the optimising outputs' slots; read back in one copy: the sizes, then the records; zeroed with them: the histograms and the flag
-    // of the gather --, then the stages' buffers
-    const uint32_t un = (uint32_t)n;
-    std::vector<int32_t> slot_of(un, -1);
-    std::vector<jpeg::OptSlot> slots;
-    for (uint32_t f = 0; f < un; f++)
-        if (outputs[f].optimize) {
-            slot_of[f] = (int32_t)slots.size();
-            slots.push_back(jpeg::OptSlot{f, sg.nc == 1 ? 2u : 4u});
-        }
-    const size_t nslots = slots.size();
-    const size_t o_im = 0, o_first = o_im + align256((size_t)un * sizeof(Image)), o_tabs = o_first + align256((size_t)jpeg::kWorkLists * (un + 1) * 4);
-    const size_t o_slotof = o_tabs + align256((size_t)un * sizeof(Tables)), o_slots = o_slotof + align256((size_t)un * 4);
-    const size_t o_sizes = o_slots + align256((nslots + 1) * sizeof(jpeg::OptSlot));
-    const size_t o_rec = o_sizes + align256((size_t)un * 8), o_hist = o_rec + align256(nslots * sizeof(jpeg::DhtRecord));
-    const size_t o_flag = o_hist + align256(nslots * sizeof(jpeg::Hist)), head = o_flag + 256;
-    const size_t back_bytes = nslots ? o_rec + nslots * sizeof(jpeg::DhtRecord) - o_sizes : (size_t)un * 8;
-    std::vector<uint8_t> up(o_sizes, 0);  // (pageable, as the decoder's upload below: alive until the call's last synchronisation)
-    Image* im = (Image*)(up.data() + o_im);
-    uint32_t* first = (uint32_t*)(up.data() + o_first);
-    for (uint32_t f = 0; f < un; f++) {
-        im[f].img = nullptr, im[f].pitch = 0, im[f].g = c.geoms[f], im[f].tab = f;
-        make_tables(ps, ((Tables*)(up.data() + o_tabs))[f]);
-    }
-    const jpeg::Totals t = jpeg::place_regions(im, un, first);
-    std::memcpy(up.data() + o_slotof, slot_of.data(), (size_t)un * 4);
-    if (nslots)
-        std::memcpy(up.data() + o_slots, slots.data(), nslots * sizeof(jpeg::OptSlot));
-    const size_t raw_bytes = align256(t.pieces * jpeg::kPiece + 16);
-    const size_t o_coef = head, o_bits = o_coef + align256(t.nblocks * 128), o_bitoff = o_bits + align256(t.nblocks * 4);
-    const size_t o_ibytes = o_bitoff + align256((t.nblocks + 1) * 8), o_ioff = o_ibytes + align256(t.nint * 4);
-    const size_t o_raw = o_ioff + align256((t.nint + 1) * 8), o_ffcnt = o_raw + raw_bytes, o_ffoff = o_ffcnt + align256(t.pieces * 4);
-    const size_t o_sums = o_ffoff + align256((t.pieces + 1) * 8), o_out = o_sums + align256(jpeg::sums_of(t, jpeg::kScanChunk) * 8);
-    const size_t enc_bytes = o_out + align256(t.out_bytes + 8);
-
-    std::vector<uint8_t> stage(l.up_bytes, 0);
-    jpegdec::stage_file(stage.data(), ps, l, subfirst, file);
-
-    Workspace ws(st);
-    hipError_t e = hipMallocAsync((void**)&ws.p, dec_bytes + enc_bytes, st);
-    if (e != hipSuccess)
-        return set_error(V1C_E_HIP, std::string("v1c_jpeg_transcode: hipMallocAsync: ") + hipGetErrorString(e));
-    uint8_t* enc = ws.p + dec_bytes;
-    const jpegdec::Args a = jpegdec::args_of(ps, l, nsub, S, ws.p, ws.p + l.up_bytes, (uint32_t*)(ws.p + l.up_bytes + l.o_flags), nullptr, 0, 3);
-    jpeg::Batch b{};
-    b.im = (const Image*)(enc + o_im), b.first = (const uint32_t*)(enc + o_first), b.tabs = (const Tables*)(enc + o_tabs);
-    b.n = un, b.t = t;
-    b.sizes = (uint64_t*)(enc + o_sizes);
-    b.buf.coef = (int16_t*)(enc + o_coef), b.buf.bits = (uint32_t*)(enc + o_bits), b.buf.bitoff = (uint64_t*)(enc + o_bitoff);
-    b.buf.ibytes = (uint32_t*)(enc + o_ibytes), b.buf.ioff = (uint64_t*)(enc + o_ioff), b.buf.raw = (uint32_t*)(enc + o_raw);
-    b.buf.ffcnt = (uint32_t*)(enc + o_ffcnt), b.buf.ffoff = (uint64_t*)(enc + o_ffoff), b.buf.sums = (uint64_t*)(enc + o_sums);
-    b.buf.out = enc + o_out;
-    jpeg::OptBatch o{};
-    o.slot_of = (const int32_t*)(enc + o_slotof), o.slots = (const jpeg::OptSlot*)(enc + o_slots), o.nslots = (uint32_t)nslots;
-    o.hist = (jpeg::Hist*)(enc + o_hist), o.rec = (jpeg::DhtRecord*)(enc + o_rec), o.tabs = (Tables*)(enc + o_tabs);
-    uint32_t* xflag = (uint32_t*)(enc + o_flag);
-
-    // the decode up to the coefficients, then the DC scan and the gathers; what comes back: a round's flag, then the two verdicts
-    uint32_t back[2] = {0, 0};
-    e = hipMemcpyAsync(ws.p, stage.data(), l.up_bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(enc, up.data(), o_sizes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(a.flags, 0, 8, st);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(a.flags + 2, 0xff, 4, st);  // kNoError
-    if (e == hipSuccess)
-        e = hipMemsetAsync(a.u, 0, l.u_bytes, st);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(a.coef, 0, l.coef_bytes, st);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(b.buf.raw, 0, raw_bytes, st);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(b.sizes, 0, head - o_sizes, st);
-    if (e == hipSuccess)
-        e = jpegdec::launch_unstuff(a, st);
-    if (e == hipSuccess)
-        e = jpegdec::launch_sync_init(a, st);
-    // the rounds: at most nsub + 1, since round r fixes the first r entry states of every segment for good
-    uint32_t r = 0;
-    while (e == hipSuccess) {
-        r++;
-        e = jpegdec::launch_sync_round(a, r, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(back, a.flags + (r & 1u), 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(st);
-        if (e != hipSuccess || back[0] == 0 || r > nsub)
-            break;
-    }
-    if (report)
-        report->rounds = r;
-    if (e == hipSuccess)
-        e = jpegdec::launch_write(a, r, st);
-    // (Unlike v1c_jpeg_decode, which reads the verdict before its pixel stage, the DC scan and the gathers are queued before the
-    //  decoder's error word is read: one synchronisation brings it together with the gather's range flag.  On a damaged scan they run
-    //  over whatever the last pass left; that is safe -- every index comes from the geometry, never from the data, and every load stays
-    //  inside the zeroed store -- and the encoder's chain, whose bounds do depend on the data, is launched only behind both verdicts.)
-    if (e == hipSuccess)
-        e = launch_dc(a, st);
-    for (uint32_t f = 0; f < un && e == hipSuccess; f++) {
+        out.push_back(jpegx::output_of(outputs[i], c.geoms[(size_t)i], c.ps, false));
+    const jpegx::Gather gather = [&c](uint32_t f, const std::vector<jpegdec::Args>& dec, int16_t* dst, uint32_t* flag, hipStream_t st) {
         GatherArgs ga{};
-        ga.src = a.coef, ga.dcoff = a.dcoff, ga.sg = sg;
-        ga.dst = b.buf.coef + (size_t)im[f].blk0 * 64, ga.dst_mcux = im[f].g.mcux, ga.dst_nblocks = im[f].g.nblocks;
-        ga.flag = xflag, ga.regions = c.lists[f];
-        e = launch_gather(ga, st);
-    }
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(&back[0], a.flags + 2, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(&back[1], xflag, 4, hipMemcpyDeviceToHost, st);
-    const hipError_t ev = hipStreamSynchronize(st);  // (also on an error above: nothing of this call reads the host's buffers after it)
-    if (e == hipSuccess)
-        e = ev;
-    if (e != hipSuccess)
-        return set_error(V1C_E_HIP, std::string("v1c_jpeg_transcode (decode): ") + hipGetErrorString(e));
-    if (back[0] != jpegdec::kNoError) {
-        if (report)
-            report->error_pos = back[0];
-        return set_error(V1C_E_CORRUPT, "v1c_jpeg_transcode: the entropy-coded data is damaged at bit " + std::to_string(back[0]) +
-                                            " of the unstuffed scan");
-    }
-    if (back[1] != 0)
-        return set_error(V1C_E_UNSUPPORTED, "v1c_jpeg_transcode: a coefficient outside what 8-bit samples give (AC beyond +-1023 or DC outside "
-                                            "-1024 ... 1023): the encoder's tables do not code it");
-
-    // the encoder's chain and its two synchronisations
-    std::vector<uint8_t> got(back_bytes, 0);
-    e = launch_encode_coef(b, nslots ? &o : nullptr, first, st);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(got.data(), b.sizes, back_bytes, hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);  // 1: the sizes and the records
-    if (e == hipSuccess)
-        e = es;
-    if (e != hipSuccess)
-        return set_error(V1C_E_HIP, std::string("v1c_jpeg_transcode (encode): ") + hipGetErrorString(e));
-    const uint64_t* sizes = (const uint64_t*)got.data();
-    for (uint32_t f = 0; f < un; f++)
-        if (sizes[f] == 0 || sizes[f] > jpeg::scan_bound(im[f].g))
-            return set_error(V1C_E_HIP, "v1c_jpeg_transcode: internal size estimate exceeded");
-    for (uint32_t f = 0; f < un && e == hipSuccess; f++)
-        e = hipMemcpyAsync(outputs[f].out_host, b.buf.out + im[f].out0, sizes[f], hipMemcpyDeviceToHost, st);
-    const hipError_t ec = hipStreamSynchronize(st);  // 2: the scans
-    if (e == hipSuccess)
-        e = ec;
-    if (e != hipSuccess)
-        return set_error(V1C_E_HIP, std::string("v1c_jpeg_transcode (copy): ") + hipGetErrorString(e));
-    for (uint32_t f = 0; f < un; f++) {
-        outputs[f].size = sizes[f];
-        if (slot_of[f] >= 0)
-            outputs[f].dht_size = jpeg::dht_body(((const jpeg::DhtRecord*)(got.data() + (o_rec - o_sizes)))[slot_of[f]], outputs[f].dht);
-    }
-    return V1C_OK;
+        ga.src = dec[0].coef, ga.dcoff = dec[0].dcoff, ga.sg = c.ps.g;
+        ga.dst = dst, ga.dst_mcux = c.geoms[f].mcux, ga.dst_nblocks = c.geoms[f].nblocks;
+        ga.flag = flag, ga.regions = c.lists[f];
+        return launch_gather(ga, st);
+    };
+    return jpegx::run("v1c_jpeg_transcode", false, device, stream, {jpegx::Source{&c.ps, file}}, S, out, gather, report);
 }

@@ -95,23 +95,7 @@ inline std::vector<uint8_t> annex_k_dht(uint32_t nc)
     return b;
 }
 
-// whether a DHT body is whole tables in the segment's order: the two of one component, or the four of three
-inline bool whole_tables(const uint8_t* dht, uint32_t dht_size, uint32_t nc)
-{
-    const uint8_t ids[4] = {0x00, 0x10, 0x01, 0x11};
-    uint32_t at = 0, tables = 0;
-    while (at < dht_size && tables < 4) {
-        if (dht[at] != ids[tables] || at + 17 > dht_size)
-            return false;
-        uint32_t nsym = 0;
-        for (int i = 0; i < 16; i++)
-            nsym += dht[at + 1 + i];
-        if (nsym < 1 || nsym > 256)
-            return false;
-        at += 17 + nsym, tables++;
-    }
-    return at == dht_size && tables == (nc == 1 ? 2u : 4u);
-}
+using jpeg::whole_tables;  // the rule of a DHT body a caller hands back: the encoder's (jpeg_host.hpp), for the callers of this header
 
 // SOI, APP0 (JFIF 1.01, aspect 1:1), DQT, SOF, DHT, DRI, SOS of an output of geometry g cut from the parsed file: the file's
 // quantisation tables as table 0 (luminance) and table 1 (chrominance), its sampling factors, the DHT body `dht` (NULL: the Annex K

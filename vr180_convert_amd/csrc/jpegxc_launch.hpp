@@ -1,4 +1,5 @@
-// jpegxc_launch.hpp -- launchers of the lossless JPEG transcoder (kernels_jpegxc.hip), called by the C ABI in jpegxc.hip: the DC scan
+// jpegxc_launch.hpp -- launchers of the lossless JPEG transcoder (kernels_jpegxc.hip), called by the C ABI in jpegxc.hip and by the
+// lossless entries' chain (jpegx_chain.hpp): the DC scan
 // of a decoded file without its pixel stage, the gather of an output's blocks from the decoder's coefficient store into the encoder's,
 // and the encoder's chain from a filled coefficient store on.
 #pragma once

@@ -19,8 +19,7 @@ from typing import Any, Sequence
 
 from . import _native
 from .jpeg_decode_device import _Report, _bytes_of, _check
-from .jpeg_device import DHT_MAX
-from .jpeg_transcode_device import HEADER_XC_MAX, MAX_OUTPUTS, MAX_REGIONS, _restart, probe_mcu
+from .jpeg_transcode_device import HEADER_XC_MAX, MAX_OUTPUTS, MAX_REGIONS, _output_fields, _restart, _run_outputs, probe_mcu
 
 MAX_SOURCES = 4     # V1C_JPEG_XF_MAX_SOURCES
 
@@ -42,9 +41,7 @@ class XfRegion(C.Structure):
 
 class XfOutput(C.Structure):
     """``v1c_jpeg_xf_output`` (include/vr180_remap.h)"""
-    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("restart_mcus", C.c_int32), ("optimize", C.c_int32), ("nregions", C.c_int32),
-                ("reserved", C.c_int32), ("regions", C.POINTER(XfRegion)), ("out_host", C.c_void_p), ("capacity", C.c_uint64),
-                ("size", C.c_uint64), ("dht_size", C.c_uint32), ("dht", C.c_uint8 * DHT_MAX)]
+    _fields_ = _output_fields(XfRegion)
 
 
 _last: dict = {}
@@ -93,29 +90,18 @@ def compose_regions(sources: Sequence[Any], outputs: Sequence[dict], *, device: 
         o.restart_mcus = _restart(spec.get("restart_mcus"), o.width, mw)
         o.optimize, o.nregions, o.regions = int(bool(spec.get("optimize", False))), len(regs), arr
     _check(lib.v1c_jpeg_compose_check(ns, srcs, n, outs, None), "v1c_jpeg_compose")
-    # (the device only from here on)
-    from .jpeg_device import _host_buffer
-    from .remapper import _device, _stream_ptr
-
-    dev = _device(device)
-    bounds = [int(lib.v1c_jpeg_compose_bound(datas[0], len(datas[0]), o.width, o.height, o.restart_mcus)) for o in outs]
-    buf = _host_buffer(dev, sum(bounds))
-    at = 0
-    for o, b in zip(outs, bounds):
-        o.out_host, o.capacity = buf.data_ptr() + at, b
-        at += b
     reps = (_Report * ns)()
-    _check(lib.v1c_jpeg_compose(dev.index, _stream_ptr(dev), ns, srcs, n, outs, int(subseq_bits), reps), "v1c_jpeg_compose")
-    host, at, files = buf.numpy(), 0, []
-    for o, b, r0 in zip(outs, bounds, first):
-        head = (C.c_uint8 * HEADER_XC_MAX)()
-        d = datas[r0[0]]
-        m = lib.v1c_jpeg_header_xf(d, len(d), o.width, o.height, o.restart_mcus, int(bool(r0[1] & _TRANSPOSE)), o.dht if o.optimize else None,
-                                   o.dht_size, head, HEADER_XC_MAX)
-        if m < 0:
-            _check(int(m), "v1c_jpeg_header_xf")
-        files.append(bytes(head[:m]) + host[at:at + int(o.size)].tobytes() + b"\xff\xd9")
-        at += b
+
+    def header(i: int, o: XfOutput, head: Any) -> int:
+        source, code = first[i][:2]  # (region 0's file and transform: whose tables the output has)
+        d = datas[source]
+        return lib.v1c_jpeg_header_xf(d, len(d), o.width, o.height, o.restart_mcus, int(bool(code & _TRANSPOSE)), o.dht if o.optimize else None,
+                                      o.dht_size, head, HEADER_XC_MAX)
+
+    files = _run_outputs(
+        outs, device, lambda o: lib.v1c_jpeg_compose_bound(datas[0], len(datas[0]), o.width, o.height, o.restart_mcus),
+        lambda index, stream: _check(lib.v1c_jpeg_compose(index, stream, ns, srcs, n, outs, int(subseq_bits), reps), "v1c_jpeg_compose"),
+        header, "v1c_jpeg_header_xf")
     _last.clear()
     _last.update(sources=[dict(segments=r.segments, subsequences=r.subsequences, rounds=r.rounds) for r in reps], sizes=[int(o.size) for o in outs])
     return files

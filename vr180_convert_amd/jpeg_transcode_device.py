@@ -30,11 +30,16 @@ class XcRegion(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("src_x", "src_y", "nx", "ny", "dst_x", "dst_y")]
 
 
+def _output_fields(region: type) -> list:
+    """the fields of ``v1c_jpeg_xc_output`` and ``v1c_jpeg_xf_output`` (include/vr180_remap.h), which differ in their regions' type"""
+    return [("width", C.c_int32), ("height", C.c_int32), ("restart_mcus", C.c_int32), ("optimize", C.c_int32), ("nregions", C.c_int32),
+            ("reserved", C.c_int32), ("regions", C.POINTER(region)), ("out_host", C.c_void_p), ("capacity", C.c_uint64),
+            ("size", C.c_uint64), ("dht_size", C.c_uint32), ("dht", C.c_uint8 * DHT_MAX)]
+
+
 class XcOutput(C.Structure):
     """``v1c_jpeg_xc_output`` (include/vr180_remap.h)"""
-    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("restart_mcus", C.c_int32), ("optimize", C.c_int32), ("nregions", C.c_int32),
-                ("reserved", C.c_int32), ("regions", C.POINTER(XcRegion)), ("out_host", C.c_void_p), ("capacity", C.c_uint64),
-                ("size", C.c_uint64), ("dht_size", C.c_uint32), ("dht", C.c_uint8 * DHT_MAX)]
+    _fields_ = _output_fields(XcRegion)
 
 
 _last: dict = {}
@@ -63,6 +68,33 @@ def _restart(restart_mcus: Any, width: int, mw: int) -> int:
     return r
 
 
+def _run_outputs(outs: Any, device: Any, bound: Any, call: Any, header: Any, header_name: str) -> list[bytes]:
+    """What ``transcode_regions`` and ``compose_regions`` do behind their host-only checks, the device only from here on: one host
+    buffer carved into every output's ``out_host`` by ``bound(o)``, the entry by ``call(device index, stream)``, and every output's
+    file -- the header that ``header(i, o, head)`` writes into the ``HEADER_XC_MAX`` bytes of ``head`` (returning their number, or the
+    code of ``header_name``), its scan and EOI."""
+    from .jpeg_device import _host_buffer
+    from .remapper import _device, _stream_ptr
+
+    dev = _device(device)
+    bounds = [int(bound(o)) for o in outs]
+    buf = _host_buffer(dev, sum(bounds))
+    at = 0
+    for o, b in zip(outs, bounds):
+        o.out_host, o.capacity = buf.data_ptr() + at, b
+        at += b
+    call(dev.index, _stream_ptr(dev))
+    host, at, files = buf.numpy(), 0, []
+    for i, (o, b) in enumerate(zip(outs, bounds)):
+        head = (C.c_uint8 * HEADER_XC_MAX)()
+        m = header(i, o, head)
+        if m < 0:
+            _check(int(m), header_name)
+        files.append(bytes(head[:m]) + host[at:at + int(o.size)].tobytes() + b"\xff\xd9")
+        at += b
+    return files
+
+
 def transcode_regions(data_or_path: Any, outputs: Sequence[dict], *, device: Any = None) -> list[bytes]:
     """The general call: every output is ``{"width", "height", "regions": [(src_x, src_y, nx, ny, dst_x, dst_y), ...]}`` with the regions
     in MCUs, and optionally ``"restart_mcus"`` (None: one MCU row; 0: none) and ``"optimize"``.  Returns every output's file.  All
@@ -85,28 +117,12 @@ def transcode_regions(data_or_path: Any, outputs: Sequence[dict], *, device: Any
         o.restart_mcus = _restart(spec.get("restart_mcus"), o.width, mw)
         o.optimize, o.nregions, o.regions = int(bool(spec.get("optimize", False))), len(regs), arr
     _check(lib.v1c_jpeg_transcode_check(data, len(data), n, outs, None), "v1c_jpeg_transcode")
-    # (the device only from here on)
-    from .jpeg_device import _host_buffer
-    from .remapper import _device, _stream_ptr
-
-    dev = _device(device)
-    bounds = [int(lib.v1c_jpeg_transcode_bound(data, len(data), o.width, o.height, o.restart_mcus)) for o in outs]
-    buf = _host_buffer(dev, sum(bounds))
-    at = 0
-    for o, b in zip(outs, bounds):
-        o.out_host, o.capacity = buf.data_ptr() + at, b
-        at += b
     rep = _Report()
-    _check(lib.v1c_jpeg_transcode(dev.index, _stream_ptr(dev), data, len(data), n, outs, 0, C.byref(rep)), "v1c_jpeg_transcode")
-    host, at, files = buf.numpy(), 0, []
-    for o, b in zip(outs, bounds):
-        head = (C.c_uint8 * HEADER_XC_MAX)()
-        m = lib.v1c_jpeg_header_xc(data, len(data), o.width, o.height, o.restart_mcus, o.dht if o.optimize else None, o.dht_size, head,
-                                   HEADER_XC_MAX)
-        if m < 0:
-            _check(int(m), "v1c_jpeg_header_xc")
-        files.append(bytes(head[:m]) + host[at:at + int(o.size)].tobytes() + b"\xff\xd9")
-        at += b
+    files = _run_outputs(
+        outs, device, lambda o: lib.v1c_jpeg_transcode_bound(data, len(data), o.width, o.height, o.restart_mcus),
+        lambda index, stream: _check(lib.v1c_jpeg_transcode(index, stream, data, len(data), n, outs, 0, C.byref(rep)), "v1c_jpeg_transcode"),
+        lambda i, o, head: lib.v1c_jpeg_header_xc(data, len(data), o.width, o.height, o.restart_mcus, o.dht if o.optimize else None,
+                                                  o.dht_size, head, HEADER_XC_MAX), "v1c_jpeg_header_xc")
     _last.clear()
     _last.update(segments=rep.segments, subsequences=rep.subsequences, rounds=rep.rounds, sizes=[int(o.size) for o in outs])
     return files
