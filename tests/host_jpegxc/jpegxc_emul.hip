@@ -18,6 +18,8 @@ namespace je = v1c::jpeg;
 
 namespace {
 
+uint32_t g_error_bit = 0xffffffffu;  // of the last call: the bit, where the last pass of a decode refused it (the composer's harness sets it too)
+
 // An output as the harness takes it: width, height, restart_mcus, optimize, nregions, then six words per region.  Returns the words
 // read, or 0 where the list ends early.
 size_t read_output(const int32_t* spec, size_t left, v1c_jpeg_xc_output& o, std::vector<v1c_jpeg_xc_region>& regions)
@@ -114,6 +116,7 @@ int encode_coef(const je::Geom& g, const std::vector<int16_t>& coef, bool optimi
 int transcode(const uint8_t* file, uint64_t size, uint32_t S, const int32_t* spec, size_t nspec, int n, uint8_t* files, uint64_t capacity,
               uint64_t* sizes)
 {
+    g_error_bit = 0xffffffffu;
     if (n < 1 || n > V1C_JPEG_XC_MAX_OUTPUTS)
         return V1C_E_INVALID;
     std::vector<v1c_jpeg_xc_output> outs((size_t)n);
@@ -144,8 +147,10 @@ int transcode(const uint8_t* file, uint64_t size, uint32_t S, const int32_t* spe
     }
     Run d;
     rc = run(file, size, S ? S : kDefaultSubseqBits, d);
-    if (rc == 3)
+    if (rc == 3) {
+        g_error_bit = d.err;
         return V1C_E_CORRUPT;
+    }
     if (rc != 0)
         return -101;
     const Geom& sg = d.ps.g;
@@ -210,6 +215,9 @@ int jxc_emul_transcode(const uint8_t* file, uint64_t size, uint32_t S, const int
 {
     return transcode(file, size, S, spec, (size_t)nspec, n, files, capacity, sizes);
 }
+
+// the bit of the unstuffed scan that the last call's V1C_E_CORRUPT of a last pass names
+uint32_t jxc_emul_error_bit() { return g_error_bit; }
 
 // the source block of every block of an output of dst_mcux x dst_mcuy MCUs (kNone where no region holds it): nregions x 6 words
 void jxc_emul_source_blocks(const int32_t* regions, int nregions, uint32_t src_mcux, uint32_t dst_mcux, uint32_t dst_mcuy, uint32_t bpm, uint32_t* out)

@@ -39,6 +39,7 @@ int compose(const uint8_t* blob, const uint64_t* sizes, int nsources, uint32_t S
 {
     if (damaged)
         *damaged = -1;
+    g_error_bit = 0xffffffffu;
     if (nsources < 1 || nsources > V1C_JPEG_XF_MAX_SOURCES || n < 1 || n > V1C_JPEG_XC_MAX_OUTPUTS)
         return V1C_E_INVALID;
     std::vector<v1c_jpeg_xf_output> outs((size_t)n);
@@ -79,6 +80,7 @@ int compose(const uint8_t* blob, const uint64_t* sizes, int nsources, uint32_t S
     for (int i = 0; i < nsources; i++) {
         rc = run(file[(size_t)i], sizes[i], S ? S : kDefaultSubseqBits, d[(size_t)i]);
         if (rc == 3) {
+            g_error_bit = d[(size_t)i].err;
             if (damaged)
                 *damaged = i;
             return V1C_E_CORRUPT;

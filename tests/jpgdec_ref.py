@@ -398,7 +398,7 @@ def dc_values(s, coef):
     d = np.zeros(s.nblocks, np.int64)
     d[pos] = coef[:, 0]
     ex = np.concatenate([[0], np.cumsum(d)])
-    out[:, 0] = (ex[pos + 1] - ex[pos0]).astype(np.int16)  # (wraps where a corrupt stream overflows: unspecified output)
+    out[:, 0] = (ex[pos + 1] - ex[pos0]).astype(np.int16)  # (the low 16 bits, signed: INTEGRATION.md section 8 item 7; only a damaged stream wraps)
     return out
 
 

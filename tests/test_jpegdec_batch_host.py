@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import jpgdec_cases as DC
+import jpgdmg_cases as M
 
 ROOT = Path(__file__).resolve().parents[1]
 HARNESS = ROOT / "tests" / "host_jpegdec_batch" / "jpegdec_batch_emul.hip"
@@ -208,7 +209,8 @@ def test_the_batchs_last_round_as_every_files_parity_changes_nothing(tmp_path):
 # ---- sanitizers -----------------------------------------------------------------------------------------------------------------------
 def test_standalone_sanitizer_run(tmp_path):
     """the host build as a program of its own under the address and undefined-behaviour sanitizers: the mixed batch with the corrupt and
-    the unsupported files in it, forwards, reversed and cut into chunks; any report fails the run"""
+    the unsupported files and every damaged scan of tests/jpgdmg_cases.py in it, forwards, reversed and cut into chunks; any report
+    fails the run"""
     exe = tmp_path / "jpegdec_batch_san"
     subprocess.run(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fno-fast-math", "-DJDEC_MAIN", "-Xarch_host",
                     "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-o", str(exe), str(HARNESS)], check=True,
@@ -225,13 +227,19 @@ def test_standalone_sanitizer_run(tmp_path):
         p = tmp_path / f"cut_{n}.jpg"
         p.write_bytes(base[:n])
         files[str(p)] = "cut"
+    # the damaged scans of tests/jpgdmg_cases.py, which do reach the entropy decoder: every file's status is the restatement's class
+    for k, x in enumerate(M.sequential_cases()):
+        p = tmp_path / f"dmg_{k}.jpg"
+        p.write_bytes(x.data)
+        files[str(p)] = M.verdict(x.name, 256, False).what
     r = subprocess.run([str(exe), *files], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
     lines = [l for l in r.stdout.strip().splitlines() if not l.startswith("batch ")]
     assert len(lines) == 2 * 3 * len(files)
     for line in lines:
         path, rc = line.split(" S=")[0], int(line.split("rc=")[1].split()[0])
-        assert rc in {"ok": (0,), "unsup": (1,), "bad": (2, 3), "cut": (2, 3)}[files[path]], line
+        assert rc in {"ok": (0,), "unsup": (1,), "bad": (2, 3), "cut": (2, 3), "decoded": (0,), "unsupported": (1,), "parse": (2,),
+                      "refused": (3,)}[files[path]], line
     chunks = [int(l.split("chunks=")[1]) for l in r.stdout.splitlines() if l.startswith("batch ")]
     assert chunks[0] == chunks[1] == 1 and chunks[2] > 3
 

@@ -14,6 +14,7 @@ import jpg_cases as PC
 import jpg_ref as R
 import jpgdec_cases as DC
 import jpgdec_ref as D
+import jpgdmg_cases as M
 
 ROOT = Path(__file__).resolve().parents[1]
 HARNESS = ROOT / "tests" / "host_jpegdec" / "jpegdec_emul.hip"
@@ -242,7 +243,8 @@ def test_corrupt_files_on_the_host_build(emul):
 
 def test_standalone_sanitizer_run(tmp_path):
     """the host build as a program of its own under the address and undefined-behaviour sanitizers: every case, the unsupported and
-    the corrupt ones included, from heap copies of the files' exact sizes; any report fails the run"""
+    the corrupt ones included, and every damaged scan of tests/jpgdmg_cases.py, from heap copies of the files' exact sizes; any report
+    fails the run"""
     exe = tmp_path / "jpegdec_san"
     subprocess.run(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fno-fast-math", "-DJDEC_MAIN", "-Xarch_host",
                     "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-o", str(exe), str(HARNESS)], check=True,
@@ -259,13 +261,19 @@ def test_standalone_sanitizer_run(tmp_path):
         p = tmp_path / f"cut_{n}.jpg"
         p.write_bytes(base[:n])
         files[str(p)] = "cut"
+    # the damaged scans of tests/jpgdmg_cases.py, which do reach the entropy decoder: the exit code is the restatement's class
+    for k, x in enumerate(M.sequential_cases()):
+        p = tmp_path / f"dmg_{k}.jpg"
+        p.write_bytes(x.data)
+        files[str(p)] = M.verdict(x.name, 256, False).what
     r = subprocess.run([str(exe), *files], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
     lines = r.stdout.strip().splitlines()
     assert len(lines) == 2 * len(files)
     for line in lines:
         path, rc = line.split(" S=")[0], int(line.split("rc=")[1].split()[0])
-        want = {"ok": (0,), "unsup": (1,), "bad": (2, 3), "cut": (2, 3)}[files[path]]
+        want = {"ok": (0,), "unsup": (1,), "bad": (2, 3), "cut": (2, 3), "decoded": (0,), "unsupported": (1,), "parse": (2,),
+                "refused": (3,)}[files[path]]
         assert rc in want, line
 
 

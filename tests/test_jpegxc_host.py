@@ -15,6 +15,7 @@ import jpg_opt_ref as O
 import jpg_ref as R
 import jpgdec_cases as JC
 import jpgdec_ref as D
+import jpgdmg_cases as M
 import jpgxc_cases as K
 import jpgxc_ref as X
 
@@ -348,7 +349,8 @@ def test_python_layer_refuses_before_any_device_call(monkeypatch):
 # ---- the stand-alone sanitizer run -----------------------------------------------------------------------------------------------------
 def test_standalone_sanitizer_run(tmp_path):
     """the host build as a program of its own under the address and undefined-behaviour sanitizers: every supported case, the refused
-    and the corrupt ones, and one file truncated at every length, from heap copies of exact sizes; any report fails the run"""
+    and the corrupt ones, one file truncated at every length and every damaged scan of tests/jpgdmg_cases.py, from heap copies of exact
+    sizes; any report fails the run"""
     exe = tmp_path / "jpegxc_san"
     subprocess.run(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fno-fast-math", "-DJXC_MAIN", "-Xarch_host",
                     "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-o", str(exe), str(HARNESS)], check=True,
@@ -372,6 +374,10 @@ def test_standalone_sanitizer_run(tmp_path):
     cuts = list(range(0, 700, 7)) + list(range(700, len(data), 41))
     for n in cuts:
         add(data[:n], outputs, -5, X.Source(data))
+    # the damaged scans of tests/jpgdmg_cases.py, which do reach the entropy decoder, as the source of a whole-image transcode
+    for x in M.sequential_cases():
+        out, code, _ = M.transcode_want(x.name)
+        add(x.data, [out], code, M.shape_of(x))
     manifest = tmp_path / "manifest.txt"
     manifest.write_text("\n".join(lines) + "\n")
     r = subprocess.run([str(exe), str(manifest)], capture_output=True, text=True, timeout=600)

@@ -18,6 +18,7 @@ import jpg_opt_ref as O
 import jpg_ref as R
 import jpgdec_cases as JC
 import jpgdec_ref as D
+import jpgdmg_cases as M
 import jpgxc_cases as XK
 import jpgxc_ref as X
 import jpgxf_cases as K
@@ -506,7 +507,8 @@ def test_exif_orientation_is_read_in_both_byte_orders_and_applied():
 # ---- the stand-alone sanitizer run -----------------------------------------------------------------------------------------------------
 def test_standalone_sanitizer_run(tmp_path):
     """the host build as a program of its own under the address and undefined-behaviour sanitizers: every case, the refused and the
-    corrupt ones, and a second source truncated at every length, from heap copies of exact sizes; any report fails the run"""
+    corrupt ones, a second source truncated at every length and every damaged scan of tests/jpgdmg_cases.py as the second source of a
+    join, from heap copies of exact sizes; any report fails the run"""
     exe = tmp_path / "jpegxf_san"
     subprocess.run(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fno-fast-math", "-DJXF_MAIN", "-Xarch_host",
                     "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-o", str(exe), str(HARNESS)], check=True,
@@ -532,6 +534,11 @@ def test_standalone_sanitizer_run(tmp_path):
     datas, outputs = CASES["join_right_rot180_420"]
     for n in list(range(0, 700, 7)) + list(range(700, len(datas[1]), 41)):
         add([datas[0], datas[1][:n]], outputs, -5)
+    # the damaged scans of tests/jpgdmg_cases.py, which do reach the entropy decoder, as the second source of a join
+    for x in M.sequential_cases():
+        j = M.join_want(x.name)
+        if j is not None:
+            add([M.base_of(x), x.data], [j[0]], j[1])
     manifest = tmp_path / "manifest.txt"
     manifest.write_text("\n".join(lines) + "\n")
     r = subprocess.run([str(exe), str(manifest)], capture_output=True, text=True, timeout=600)

@@ -7,7 +7,7 @@ and destination views (dword-aligned or not), per-unit rotations, apply_lr pairs
 (v1c_remap_lut) on random float32 maps sprinkled with NaN, infinities, 2^15 / 2^26 / 2^31-scale values and ties of the 1/32 grid.
 
     python3 tools/fuzz.py [--seconds 300] [--seed 1] [--big 0.15] [--lut 0.15] [--hot 0.3] [--gen2 0] [--api 0.1] [--auto 0.06] [--fused 0.06] [--log gpurun_out/fuzz.log]
-                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--jpegprog 0] [--jpegxc 0] [--jpegxf 0] [--cases N]
+                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--jpegprog 0] [--jpegxc 0] [--jpegxf 0] [--jpegdmg 0] [--cases N]
 
 --wide P: that share of the cases has uint16 or float32 pixels (k_remap_wide): the chain cases above -- same grammar, views, batches, pairs,
 per-unit rotations, graph replays and the same three masks, counted in the same counters -- and the LUT cases (v1c_remap_lut_ex, nothing left
@@ -28,7 +28,11 @@ scale, radius, margin, threshold, cell, per_cell and the cap drawn off their def
 sets of 0 ... 20000 descriptors with planted copies, duplicates and ties.  A case that v1c_feat_detect refuses (working image under 33 x 33, empty
 circle) where feat_ref.refusal predicts it is correct and not counted (the summary line says how many).  --jpegprog P: that share goes through the device decoder of progressive JPEG files
 (decode_jpeg_tensor(progressive=True)) -- Pillow's progressive files and tests/jpgprog_cases.py's writer with random legal scan scripts --
-against tests/jpgprog_ref.py: pixels, scans and the rounds of every scan.  --jpegxf P: that share goes through the lossless JPEG composer (compose_regions) -- one to four random files of one kind up to 96 x 96 and one or two outputs of strips under random codes -- against tests/jpgxf_ref.py, byte for byte; a composition both sides refuse alike counts as agreement (the summary line says how many).  These shares come off the top of the
+against tests/jpgprog_ref.py: pixels, scans and the rounds of every scan.  --jpegxf P: that share goes through the lossless JPEG composer (compose_regions) -- one to four random files of one kind up to 96 x 96 and one or two outputs of strips under random codes -- against tests/jpgxf_ref.py, byte for byte; a composition both sides refuse alike counts as agreement (the summary line says how many).  --jpegdmg P: that share goes through the device JPEG decoders (v1c_jpeg_decode,
+v1c_jpeg_prog_decode) with a DAMAGED scan -- a file as --jpegdec / --jpegprog draw it, one random damage of tests/jpgdmg_cases.py's kinds (a bit
+flipped, a byte replaced, 1-3 bytes deleted or inserted, two restart segments exchanged, the scan filled) inside the entropy-coded bytes of one
+scan, a random subsequence size -- against the restatement's verdict: the code, the smallest bad bit and its scan, the rounds, and the pixels of
+damage that is still a legal stream (the summary line says how many cases were refused by the last pass, decoded, or left to the parse).  These shares come off the top of the
 case draw: with all of them at 0 every earlier seed replays as it ran.
 
 Round 5 added to the grammar: hot shapes of the chains that left the interpreter (planar fisheye -> fisheye, is_latitude_y=False, a
@@ -1116,14 +1120,13 @@ def jpegxf_case(rng, dev) -> tuple[str, int]:
     return desc, bad + abs(len(got) - len(want))
 
 
-def jpegdec_case(rng, dev) -> tuple[str, int]:
-    """the device JPEG decoder (decode_jpeg_tensor) against its restatement (jpgdec_ref.decode), the pixels byte for byte: a random
-    image up to 96 x 96 -- smooth, noise, flat, mixed -- written by Pillow (grey, 4:4:4, 4:2:2 or 4:2:0, any quality, optimised tables
-    and its restart options now and then) or by the encoder's restatement (any restart interval), decoded at a random subsequence size"""
+def jpegdec_draw(rng) -> tuple[bytes, int, str]:
+    """(file, components, description): a random image up to 96 x 96 -- smooth, noise, flat, mixed -- written by Pillow (grey, 4:4:4,
+    4:2:2 or 4:2:0, any quality, optimised tables and its restart options now and then) or by the encoder's restatement (any restart
+    interval)"""
     import jpg_cases as JC
     import jpg_ref as JR
     import jpgdec_cases as DC
-    import jpgdec_ref as DR
 
     h, w = (int(v) for v in rng.integers(1, 97, 2))
     quality = int(rng.choice([1, 10, 50, 75, 90, 95, 100])) if rng.random() < 0.7 else int(rng.integers(1, 101))
@@ -1159,6 +1162,15 @@ def jpegdec_case(rng, dev) -> tuple[str, int]:
             kw["restart_marker_rows"] = int(rng.integers(1, 4))
         data = DC.pillow(img, quality, sampling, **kw)
         how = f"Pillow {kw!r}"
+    return data, cn, f"{kind} {(h, w, cn)} seed={seed} quality={quality} sampling={sampling} {how}"
+
+
+def jpegdec_case(rng, dev) -> tuple[str, int]:
+    """the device JPEG decoder (decode_jpeg_tensor) against its restatement (jpgdec_ref.decode), the pixels byte for byte: a file of
+    ``jpegdec_draw`` decoded at a random subsequence size"""
+    import jpgdec_ref as DR
+
+    data, cn, what = jpegdec_draw(rng)
     S = int(rng.choice([0, 256, 256, 288, 512, 1024, 4096]))
     channels = 1 if cn == 1 and rng.random() < 0.5 else 3
     got = V.decode_jpeg_tensor(data, channels=channels, subseq_bits=S or None).cpu().numpy()
@@ -1167,20 +1179,17 @@ def jpegdec_case(rng, dev) -> tuple[str, int]:
     KINDS["jpegdec"] = KINDS.get("jpegdec", 0) + 1
     bad = int((got != want.pixels).sum()) if got.shape == want.pixels.shape else got.size
     bad += 0 if (rep["segments"], rep["subsequences"]) == (want.segments, want.subsequences) and rep["rounds"] <= want.rounds else 1
-    return f"JPEGDEC {kind} {(h, w, cn)} seed={seed} quality={quality} sampling={sampling} {how} subseq_bits={S} channels={channels}", bad
+    return f"JPEGDEC {what} subseq_bits={S} channels={channels}", bad
 
 
-def jpegprog_case(rng, dev) -> tuple[str, int]:
-    """the device decoder of progressive JPEG files (decode_jpeg_tensor(progressive=True)) against its restatement
-    (jpgprog_ref.decode): the pixels byte for byte, the rounds of every scan and the report.  A random image up to 64 x 64 written
-    progressive by Pillow (its own script, restart options now and then), or its coefficients written again by
-    jpgprog_cases.progressive with a random legal script -- DC interleaved, per component or in groups, random bands, point
-    transforms up to 3 with their refinements in a random order, a restart interval of its own for any scan -- decoded at a random
-    subsequence size"""
+def jpegprog_draw(rng) -> tuple[bytes, int, str]:
+    """(file, components, description): a random image up to 64 x 64 written progressive by Pillow (its own script, restart options
+    now and then), or its coefficients written again by jpgprog_cases.progressive with a random legal script -- DC interleaved, per
+    component or in groups, random bands, point transforms up to 3 with their refinements in a random order, a restart interval of its
+    own for any scan"""
     import jpg_cases as JC
     import jpgdec_cases as DC
     import jpgprog_cases as PC
-    import jpgprog_ref as PR
 
     h, w = (int(v) for v in rng.integers(1, 65, 2))
     quality = int(rng.choice([10, 50, 75, 90, 95, 100]))
@@ -1232,6 +1241,16 @@ def jpegprog_case(rng, dev) -> tuple[str, int]:
         data = PC.from_sequential(DC.pillow(img, quality, sampling), script)
         how = f"writer scans={len(script)} " + " ".join(f"{''.join(map(str, sc['comps']))}:{sc['Ss']}-{sc['Se']}:{sc['Ah']}{sc['Al']}" +
                                                            (f":dri{sc['dri']}" if sc["dri"] is not None else "") for sc in script)
+    return data, cn, f"{kind} {(h, w, cn)} seed={seed} quality={quality} sampling={sampling} {how}"
+
+
+def jpegprog_case(rng, dev) -> tuple[str, int]:
+    """the device decoder of progressive JPEG files (decode_jpeg_tensor(progressive=True)) against its restatement
+    (jpgprog_ref.decode): the pixels byte for byte, the rounds of every scan and the report, of a file of ``jpegprog_draw`` decoded
+    at a random subsequence size"""
+    import jpgprog_ref as PR
+
+    data, cn, what = jpegprog_draw(rng)
     S = int(rng.choice([0, 256, 256, 288, 512, 1024]))
     channels = 1 if cn == 1 and rng.random() < 0.5 else 3
     got = V.decode_jpeg_tensor(data, channels=channels, subseq_bits=S or None, progressive=True).cpu().numpy()
@@ -1241,7 +1260,72 @@ def jpegprog_case(rng, dev) -> tuple[str, int]:
     bad = int((got != want.pixels).sum()) if got.shape == want.pixels.shape else got.size
     bad += 0 if (rep["scans"], rep["segments"], rep["subsequences"], rep["scan_rounds"]) == (want.scans, want.segments, want.subsequences,
                                                                                              want.scan_rounds) else 1
-    return f"JPEGPROG {kind} {(h, w, cn)} seed={seed} quality={quality} sampling={sampling} {how} subseq_bits={S} channels={channels}", bad
+    return f"JPEGPROG {what} subseq_bits={S} channels={channels}", bad
+
+
+DMG = {"drawn": 0, "refused": 0, "decoded": 0, "parse": 0}  # jpegdmg cases by the restatement's verdict (parse: unsupported too)
+
+
+def jpegdmg_draw(rng) -> tuple[str, bytes, bool, int]:
+    """(description, file, whether it is progressive, subsequence size) of a --jpegdmg case: a file of ``jpegdec_draw`` or
+    ``jpegprog_draw`` with one random damage of tests/jpgdmg_cases.py's kinds inside the entropy-coded bytes of one scan (a kind the
+    file has no scan for -- two restart segments to exchange, a scan without markers to fill -- becomes a flipped bit)"""
+    import jpgdmg_cases as M
+
+    prog = bool(rng.random() < 0.4)
+    data, cn, what = (jpegprog_draw if prog else jpegdec_draw)(rng)
+    kind = str(rng.choice(M.RANDOM_KINDS))
+    seed = int(rng.integers(0, 1 << 30))
+    hurt = M.draw(data, prog, kind, np.random.default_rng(seed))
+    if hurt is None:
+        kind = "bitflip"
+        hurt = M.draw(data, prog, kind, np.random.default_rng(seed))
+    S = int(rng.choice([256, 256, 288, 512, 1024]))
+    return f"JPEGDMG {'progressive' if prog else 'sequential'} {what} damage={kind} damage_seed={seed} subseq_bits={S}", hurt, prog, S
+
+
+def jpegdmg_device(data, prog, S, h, w) -> tuple:
+    """(code, error bit, error scan, rounds, pixels) of the device through the C ABI; h, w: the output to allocate"""
+    import ctypes as C
+
+    from vr180_convert_amd import _abi, _native
+    from vr180_convert_amd.jpeg_decode_device import _Report
+
+    lib = _native.lib()
+    out = torch.zeros((h, w, 3), dtype=torch.uint8, device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+    if prog:
+        rep = _abi.JpegProgReport()
+        rc = lib.v1c_jpeg_prog_decode(0, st, data, len(data), out.data_ptr(), 3 * w, 3, S, C.byref(rep), None, 0)
+        return rc, int(rep.error_pos), int(rep.error_scan), int(rep.rounds), out.cpu().numpy()
+    rep = _Report()
+    rc = lib.v1c_jpeg_decode(0, st, data, len(data), out.data_ptr(), 3 * w, 3, S, C.byref(rep))
+    return rc, int(rep.error_pos), 0, int(rep.rounds), out.cpu().numpy()
+
+
+def jpegdmg_case(rng, dev) -> tuple[str, int]:
+    """a damaged scan through the device decoders against the restatement's verdict (jpgdmg_cases.verdict_of): the code, the smallest
+    bad bit and its scan, the rounds also of a refused file, and the pixels of damage that is still a legal stream"""
+    import jpgdmg_cases as M
+
+    desc, data, prog, S = jpegdmg_draw(rng)
+    want = M.verdict_of(data, S, prog)
+    DMG["drawn"] += 1
+    DMG[want.what if want.what in ("refused", "decoded") else "parse"] += 1
+    KINDS["jpegdmg"] = KINDS.get("jpegdmg", 0) + 1
+    h, w = want.pixels.shape[:2] if want.what == "decoded" else (8, 8)
+    if want.what == "refused":
+        s = (M.P.parse if prog else M.D.parse)(data)
+        h, w = s.h, s.w
+    rc, bit, scan, rounds, px = jpegdmg_device(data, prog, S, h, w)
+    bad = 0 if rc == {"decoded": 0, "unsupported": -2, "parse": -5, "refused": -5}[want.what] else 1
+    if want.what in ("decoded", "refused"):
+        bad += 0 if rounds == want.rounds else 1
+    if want.what == "refused":
+        bad += 0 if (bit, scan) == (want.bit, want.scan) else 1
+    if want.what == "decoded" and rc == 0:
+        bad += int((px != want.pixels).sum())
+    return f"{desc} restatement: {want.what} bit={want.bit} scan={want.scan} rounds={want.rounds}; device: rc={rc} bit={bit} scan={scan} rounds={rounds}", bad
 
 
 FEAT = {"drawn": 0, "refused": 0}  # feat cases drawn / of them refused by v1c_feat_detect as feat_ref.refusal predicts (not counted)
@@ -1413,6 +1497,7 @@ def main() -> int:
     ap.add_argument("--jpegprog", type=float, default=0.0, help="share of cases through the device decoder of progressive JPEG files (decode_jpeg_tensor(progressive=True)) against jpgprog_ref.decode")
     ap.add_argument("--jpegxc", type=float, default=0.0, help="share of cases through the lossless JPEG transcoder (transcode_regions: crops, splits, swaps) against jpgxc_ref.transcode")
     ap.add_argument("--jpegxf", type=float, default=0.0, help="share of cases through the lossless JPEG composer (compose_regions: joins, rotations, flips of up to four files) against jpgxf_ref.compose")
+    ap.add_argument("--jpegdmg", type=float, default=0.0, help="share of cases through the device JPEG decoders with one random damage inside a scan, against the verdict of tests/jpgdmg_cases.py")
     ap.add_argument("--cases", type=int, default=None, help="stop after this many cases (before --seconds runs out)")
     ap.add_argument("--feat", type=float, default=0.0, help="share of cases through the feature pipeline (features.detect / features.match) against tests/feat_ref.py")
     ap.add_argument("--only", type=int, default=None, help="run only this case number (reproduce)")
@@ -1447,9 +1532,12 @@ def main() -> int:
             r_kind = rng.random()
             wide_chain = False
             counted = True
-            rest = 1.0 - a.jpegxf
+            rest0 = 1.0 - a.jpegdmg
+            rest = rest0 - a.jpegxf
             top = rest - a.jpegxc - a.jpegprog - a.jpegopt - a.jpegbatch - a.jpegdec
-            if r_kind >= rest:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+            if r_kind >= rest0:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+                desc, bad = jpegdmg_case(rng, dev)
+            elif r_kind >= rest:
                 desc, bad = jpegxf_case(rng, dev)
             elif r_kind >= rest - a.jpegxc:
                 desc, bad = jpegxc_case(rng, dev)
@@ -1509,7 +1597,9 @@ def main() -> int:
         + (f"; wide chain cases: {WIDE_CHAIN['run']} run, {WIDE_CHAIN['not counted']} of them over 5 % masked and not counted, "
            f"{WIDE_CHAIN['masked px']} of {WIDE_CHAIN['px']} pixels masked" if WIDE_CHAIN["run"] else "")
         + (f"; feat cases: {FEAT['drawn']} drawn, {FEAT['refused']} of them refused as predicted and not counted" if FEAT["drawn"] else "")
-        + (f"; jpegxf cases: {XF['drawn']} drawn, {XF['refused']} of them refused by both sides alike" if XF["drawn"] else ""))
+        + (f"; jpegxf cases: {XF['drawn']} drawn, {XF['refused']} of them refused by both sides alike" if XF["drawn"] else "")
+        + (f"; jpegdmg cases: {DMG['drawn']} drawn, {DMG['refused']} refused by the last pass, {DMG['decoded']} decoded, {DMG['parse']} left to the parse"
+           if DMG["drawn"] else ""))
     say("kernel families of the chain cases' launch groups: " + ", ".join(f"{k} x{v}" for k, v in sorted(KINDS.items())))
     return 1 if n_bad else 0
 
