@@ -18,7 +18,7 @@ import struct
 from typing import Any, Sequence
 
 from . import _native
-from .jpeg_decode_device import _Report, _bytes_of, _check
+from .jpeg_decode_device import _Last, _Report, _bytes_of, _check
 from .jpeg_transcode_device import HEADER_XC_MAX, MAX_OUTPUTS, MAX_REGIONS, _output_fields, _restart, _run_outputs, probe_mcu
 
 MAX_SOURCES = 4     # V1C_JPEG_XF_MAX_SOURCES
@@ -44,13 +44,13 @@ class XfOutput(C.Structure):
     _fields_ = _output_fields(XfRegion)
 
 
-_last: dict = {}
+_last = _Last()
 
 
 def last_compose_report() -> dict:
-    """what the last composition did: per source the ``segments``, ``subsequences`` and ``rounds`` of its decode, and every output's
+    """what the calling thread's last composition did: per source the ``segments``, ``subsequences`` and ``rounds`` of its decode, and every output's
     scan ``sizes``"""
-    return dict(_last)
+    return _last.get()
 
 
 def transform_code(transform: Any) -> int:

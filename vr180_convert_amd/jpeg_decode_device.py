@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import logging
+import threading
 from pathlib import Path
 from typing import Any
 
@@ -36,9 +37,26 @@ class _Report(C.Structure):
                 ("error_pos", C.c_uint64)]
 
 
+class _Last(threading.local):
+    """the report of the calling thread's last call: every thread sees a dict of its own (as remapper._TLS keeps the last plans per
+    thread), so a thread that asks what its call did is not told about another thread's"""
+
+    def __init__(self) -> None:
+        self.report: dict = {}
+
+    def clear(self) -> None:
+        self.report = {}
+
+    def update(self, **kw: Any) -> None:
+        self.report.update(kw)
+
+    def get(self) -> dict:
+        return dict(self.report)
+
+
 LOG = logging.getLogger(__name__)
-_last: dict = {}
-_last_batch: dict = {}
+_last = _Last()
+_last_batch = _Last()
 
 
 class CorruptJPEG(ValueError):
@@ -151,10 +169,10 @@ def imread_tensor(path: Any, *, device: Any = None, channels: int = 3, subseq_bi
 
 
 def last_decode_report() -> dict:
-    """of the last successful decode: ``segments`` (stretches between restart markers), ``subsequences`` (lanes), ``rounds`` (launches
+    """of the calling thread's last successful decode: ``segments`` (stretches between restart markers), ``subsequences`` (lanes), ``rounds`` (launches
     until the entry states stood still) and ``path="device"``; after a progressive file the three are summed over its scans, and
     ``scans`` and ``scan_rounds`` (a list) are there too"""
-    return dict(_last)
+    return _last.get()
 
 
 def _error_of(rc: int, what: str, msg: str) -> Exception:
@@ -243,9 +261,9 @@ def imread_tensors(paths: Any, *, device: Any = None, channels: int = 3, subseq_
 
 
 def last_batch_report() -> dict:
-    """of the last ``decode_jpeg_tensors`` call: ``batch_rounds`` (round launches, summed over the chunks), ``chunks`` and ``files``, per
+    """of the calling thread's last ``decode_jpeg_tensors`` call: ``batch_rounds`` (round launches, summed over the chunks), ``chunks`` and ``files``, per
     file the dict ``last_decode_report()`` gives after a single call, or None for a file that was not decoded"""
-    return dict(_last_batch)
+    return _last_batch.get()
 
 
 def read_inputs(items: Any, *, device: Any = None, batch: bool = False, progressive: bool = False) -> list:

@@ -15,6 +15,7 @@ the pixels a reader decodes are the same, the file is smaller (``tests/jpg_opt_r
 from __future__ import annotations
 
 import ctypes as C
+import threading
 from pathlib import Path
 from typing import Any, Sequence
 
@@ -51,14 +52,20 @@ def default_restart_mcus(height: int, width: int, channels: int, subsampling: st
     return min(65535, -(-width // m))
 
 
-_pinned: dict[int, torch.Tensor] = {}  # per device: the page-locked buffer the scan lands in, grown on demand
+# Per calling thread (as remapper._TLS keeps the last plans per thread):
+#   .pinned: {device index: the page-locked buffer the thread's scans land in}, grown on demand and kept until the thread ends.  The
+#            engine call releases the GIL and the callers read views of the buffer after it, so a buffer shared between threads would
+#            hand one thread another's scan; the lossless entries (jpeg_transcode_device._run_outputs) land in the same buffer.
+#   .encode_batch: the report of the thread's last batch (last_encode_batch_report)
+_TLS = threading.local()
 
 
 def _host_buffer(dev: torch.device, nbytes: int) -> torch.Tensor:
-    buf = _pinned.get(dev.index)
+    pinned = _TLS.__dict__.setdefault("pinned", {})
+    buf = pinned.get(dev.index)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
-        _pinned[dev.index] = buf
+        pinned[dev.index] = buf
     return buf
 
 
@@ -149,13 +156,11 @@ def imwrite_jpeg_tensor(path: Any, t: torch.Tensor, *, quality: int = 95, subsam
             f.write(part)
 
 
-_last_encode_batch: dict = {"chunks": 0, "sizes": []}
-
-
 def last_encode_batch_report() -> dict:
-    """``{"chunks": ..., "sizes": [...]}`` of the last ``encode_jpeg_tensors`` / ``imwrite_jpeg_tensors`` call: the chunks the engine ran
-    (two synchronisations each) over all sub-lists, and every image's scan size"""
-    return {"chunks": _last_encode_batch["chunks"], "sizes": list(_last_encode_batch["sizes"])}
+    """``{"chunks": ..., "sizes": [...]}`` of the calling thread's last ``encode_jpeg_tensors`` / ``imwrite_jpeg_tensors`` call: the chunks
+    the engine ran (two synchronisations each) over all sub-lists, and every image's scan size"""
+    last = getattr(_TLS, "encode_batch", {"chunks": 0, "sizes": []})
+    return {"chunks": last["chunks"], "sizes": list(last["sizes"])}
 
 
 def _per_image(value: Any, n: int, name: str) -> list:
@@ -183,12 +188,12 @@ def sub_lists(bounds: Sequence[int], budget: int | None = None) -> list[tuple[in
 
 def _batch_parts(tensors: Sequence[torch.Tensor], quality: Any, subsampling: Any, restart_mcus: Any, workspace_budget: int | None,
                  optimize: Any = False):
-    """yields (index, [header, scan, EOI]) of every image, sub-list by sub-list; a scan is a view of the page-locked buffer that holds
-    until the next sub-list is encoded"""
+    """yields (index, [header, scan, EOI]) of every image, sub-list by sub-list; a scan is a view of the calling thread's page-locked
+    buffer that holds until the thread encodes the next sub-list"""
     n = len(tensors)
     qs, ss, rs = _per_image(quality, n, "quality"), _per_image(subsampling, n, "subsampling"), _per_image(restart_mcus, n, "restart_mcus")
     opts = [bool(o) for o in _per_image(optimize, n, "optimize")]
-    _last_encode_batch["chunks"], _last_encode_batch["sizes"] = 0, []
+    report = _TLS.encode_batch = {"chunks": 0, "sizes": []}
     if n == 0:
         return
     params = [_params(t, q, s, r) for t, q, s, r in zip(tensors, qs, ss, rs)]
@@ -216,7 +221,7 @@ def _batch_parts(tensors: Sequence[torch.Tensor], quality: Any, subsampling: Any
         entry = "v1c_jpeg_encode_batch_opt" if some else "v1c_jpeg_encode_batch"
         rc = getattr(lib, entry)(dev.index, _stream_ptr(dev), hi - lo, images, int(workspace_budget or 0), C.byref(chunks))
         _native.check(rc, entry)
-        _last_encode_batch["chunks"] += chunks.value
+        report["chunks"] += chunks.value
         host, at = buf.numpy(), 0
         for k in range(lo, hi):
             _, h, w, cn, q, sub, restart = params[k]
@@ -226,7 +231,7 @@ def _batch_parts(tensors: Sequence[torch.Tensor], quality: Any, subsampling: Any
                     else _header(h, w, cn, q, sub, restart))
             yield k, [head, host[at:at + size], b"\xff\xd9"]
             at += bounds[k]
-    _last_encode_batch["sizes"] = sizes
+    report["sizes"] = sizes
 
 
 def encode_jpeg_tensors(tensors: Sequence[torch.Tensor], *, quality: Any = 95, subsampling: Any = "420", restart_mcus: Any = None,

@@ -17,7 +17,7 @@ import ctypes as C
 from typing import Any, Sequence
 
 from . import _native
-from .jpeg_decode_device import _Info, _Report, _bytes_of, _check
+from .jpeg_decode_device import _Info, _Last, _Report, _bytes_of, _check
 from .jpeg_device import DHT_MAX
 
 MAX_REGIONS = 16    # V1C_JPEG_XC_MAX_REGIONS
@@ -42,12 +42,12 @@ class XcOutput(C.Structure):
     _fields_ = _output_fields(XcRegion)
 
 
-_last: dict = {}
+_last = _Last()
 
 
 def last_transcode_report() -> dict:
-    """what the last transcode did: ``segments``, ``subsequences`` and ``rounds`` of the decode, and every output's scan ``sizes``"""
-    return dict(_last)
+    """what the calling thread's last transcode did: ``segments``, ``subsequences`` and ``rounds`` of the decode, and every output's scan ``sizes``"""
+    return _last.get()
 
 
 def probe_mcu(data_or_path: Any) -> tuple[int, int, int, int]:

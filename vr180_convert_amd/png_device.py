@@ -8,6 +8,7 @@ than the host writer's (INTEGRATION.md section 6 has the contract and the measur
 from __future__ import annotations
 
 import ctypes as C
+import threading
 from pathlib import Path
 from typing import Any
 
@@ -31,14 +32,18 @@ def default_band_rows(height: int, stride: int) -> int:
     return max(1, min(height, -(-BAND_BYTES // stride)))
 
 
-_pinned: dict[int, torch.Tensor] = {}  # per device: the page-locked buffer the stream lands in, grown on demand
+# Per calling thread, .pinned: {device index: the page-locked buffer the thread's streams land in}, grown on demand and kept until the
+# thread ends.  The engine call releases the GIL and the callers read views of the buffer after it, so a buffer shared between threads
+# would hand one thread another's stream.
+_TLS = threading.local()
 
 
 def _host_buffer(dev: torch.device, nbytes: int) -> torch.Tensor:
-    buf = _pinned.get(dev.index)
+    pinned = _TLS.__dict__.setdefault("pinned", {})
+    buf = pinned.get(dev.index)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
-        _pinned[dev.index] = buf
+        pinned[dev.index] = buf
     return buf
 
 
@@ -59,7 +64,8 @@ def _image(t: torch.Tensor) -> torch.Tensor:
 
 def deflate_tensor(t: torch.Tensor, *, filter: str = "up", band_rows: int | None = None):
     """``(segments, bands)`` of a device image on the current stream: a uint8 view of the band segments (valid until the next call
-    on this device) and one ``(row0, row1, offset, size, adler32, stored)`` tuple per band."""
+    on this device from this thread: the buffer behind it belongs to the calling thread) and one ``(row0, row1, offset, size, adler32,
+    stored)`` tuple per band."""
     if filter not in FILTERS:
         raise ValueError(f"filter must be one of {sorted(FILTERS)}, not {filter!r}")
     t = _image(t)
