@@ -24,6 +24,12 @@ class Corrupt(Exception):
     """V1C_E_CORRUPT"""
 
 
+def _at(e, pos):
+    """the exception with the byte of the file the parse refuses it at (``pos``): what the product reports as error_pos"""
+    e.pos = pos
+    return e
+
+
 # ---- the host-only parse ---------------------------------------------------------------------------------------------------------------
 class Huff:
     """a DHT table: ``lut[first 16 bits] = length << 8 | symbol``, 0 where the bits start no code"""
@@ -55,7 +61,7 @@ def parse(data) -> Info:
     d = bytes(data)
     n = len(d)
     if n < 4 or d[0] != 0xFF or d[1] != 0xD8:
-        raise Corrupt("no SOI")
+        raise _at(Corrupt("no SOI"), 0)
     s = Info()
     s.q, s.dc, s.ac = [None] * 4, [None] * 4, [None] * 4
     s.restart = 0
@@ -63,58 +69,61 @@ def parse(data) -> Info:
     pos = 2
     while True:
         if pos + 1 >= n or d[pos] != 0xFF:
-            raise Corrupt("marker expected")
+            raise _at(Corrupt("marker expected"), pos)
         while pos + 1 < n and d[pos + 1] == 0xFF:
             pos += 1                                       # fill bytes
         if pos + 1 >= n:
-            raise Corrupt("file ends in a marker")
+            raise _at(Corrupt("file ends in a marker"), pos)
         m = d[pos + 1]
         pos += 2
         if m == 0x01 or 0xD0 <= m <= 0xD7:
             continue
         if m in (0xD8, 0xD9):
-            raise Corrupt("SOI / EOI before the scan")
+            raise _at(Corrupt("SOI / EOI before the scan"), pos - 2)
         if pos + 2 > n:
-            raise Corrupt("segment length")
+            raise _at(Corrupt("segment length"), pos)
         ln = _be16(d, pos)
         if ln < 2 or pos + ln > n:
-            raise Corrupt("segment length")
+            raise _at(Corrupt("segment length"), pos)
         body = d[pos + 2:pos + ln]
         if m in (0xC0, 0xC1):
             if frame is not None or len(body) < 6 or len(body) != 6 + 3 * body[5]:
-                raise Corrupt("SOF")
+                raise _at(Corrupt("SOF"), pos)
             if body[0] != 8:
-                raise Unsupported(f"{body[0]}-bit samples")
+                raise _at(Unsupported(f"{body[0]}-bit samples"), pos)
             s.h, s.w, s.nc = _be16(body, 1), _be16(body, 3), body[5]
             if s.h == 0:
-                raise Unsupported("height 0: DNL")
+                raise _at(Unsupported("height 0: DNL"), pos)
             if s.w == 0:
-                raise Corrupt("width 0")
+                raise _at(Corrupt("width 0"), pos)
             if s.nc not in (1, 3):
-                raise Unsupported(f"{s.nc} components")
+                raise _at(Unsupported(f"{s.nc} components"), pos)
             frame = [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(s.nc)]
         elif m in (0xC2, 0xC3, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xCB, 0xCC, 0xCD, 0xCE, 0xCF):
-            raise Unsupported("progressive, lossless or arithmetic")
+            raise _at(Unsupported("progressive, lossless or arithmetic"), pos)
         elif m == 0xC4:
             i = 0
             while i < len(body):
                 if i + 17 > len(body) or (body[i] >> 4) > 1 or (body[i] & 15) > 3:
-                    raise Corrupt("DHT")
+                    raise _at(Corrupt("DHT"), pos)
                 bits = body[i + 1:i + 17]
                 cnt = sum(bits)
                 if cnt > 256 or i + 17 + cnt > len(body):
-                    raise Corrupt("DHT")
+                    raise _at(Corrupt("DHT"), pos)
                 vals = body[i + 17:i + 17 + cnt]
                 if (body[i] >> 4) == 0 and any(v > 15 for v in vals):
-                    raise Corrupt("DHT: DC category above 15")
-                (s.ac if body[i] >> 4 else s.dc)[body[i] & 15] = Huff(bits, vals)
+                    raise _at(Corrupt("DHT: DC category above 15"), pos)
+                try:
+                    (s.ac if body[i] >> 4 else s.dc)[body[i] & 15] = Huff(bits, vals)
+                except Corrupt as e:
+                    raise _at(e, pos)
                 i += 17 + cnt
         elif m == 0xDB:
             i = 0
             while i < len(body):
                 pq, tq = body[i] >> 4, body[i] & 15
                 if pq > 1 or tq > 3 or i + 1 + 64 * (pq + 1) > len(body):
-                    raise Corrupt("DQT")
+                    raise _at(Corrupt("DQT"), pos)
                 t = np.zeros(64, np.int64)
                 for k in range(64):
                     t[ZIGZAG[k]] = _be16(body, i + 1 + 2 * k) if pq else body[i + 1 + k]
@@ -122,37 +131,37 @@ def parse(data) -> Info:
                 i += 1 + 64 * (pq + 1)
         elif m == 0xDD:
             if ln != 4:
-                raise Corrupt("DRI")
+                raise _at(Corrupt("DRI"), pos)
             s.restart = _be16(body, 0)
         elif m == 0xDC:
-            raise Unsupported("DNL")
+            raise _at(Unsupported("DNL"), pos)
         elif m == 0xEE and len(body) >= 12 and body[:5] == b"Adobe":
             adobe = body[11]
         elif m == 0xDA:
             if frame is None or len(body) < 1 or len(body) != 4 + 2 * body[0]:
-                raise Corrupt("SOS")
+                raise _at(Corrupt("SOS"), pos)
             if body[0] != s.nc:
-                raise Unsupported("several scans")
+                raise _at(Unsupported("several scans"), pos)
             s.td, s.ta, s.tq = [], [], []
             for i in range(s.nc):
                 if body[1 + 2 * i] != frame[i][0]:
-                    raise Unsupported("scan components out of order")
+                    raise _at(Unsupported("scan components out of order"), pos)
                 td, ta = body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15
                 if td > 3 or ta > 3 or s.dc[td] is None or s.ac[ta] is None or frame[i][3] > 3 or s.q[frame[i][3]] is None:
-                    raise Corrupt("a table the scan names is missing")
+                    raise _at(Corrupt("a table the scan names is missing"), pos)
                 s.td.append(td), s.ta.append(ta), s.tq.append(frame[i][3])
             if body[-3] != 0 or body[-2] != 63 or body[-1] != 0:
-                raise Unsupported("spectral selection or successive approximation")
+                raise _at(Unsupported("spectral selection or successive approximation"), pos)
             pos += ln
             break
         pos += ln
     if s.nc == 3 and adobe == 0:
-        raise Unsupported("Adobe transform 0: RGB")
+        raise _at(Unsupported("Adobe transform 0: RGB"), pos)
     if s.nc == 1:
         s.hs = s.vs = 1                                     # (one component: not interleaved, whatever its factors)
     else:
         if (frame[1][1], frame[1][2], frame[2][1], frame[2][2]) != (1, 1, 1, 1) or (frame[0][1], frame[0][2]) not in ((1, 1), (2, 1), (2, 2)):
-            raise Unsupported("sampling factors")
+            raise _at(Unsupported("sampling factors"), pos)
         s.hs, s.vs = frame[0][1], frame[0][2]
     s.ny = s.hs * s.vs
     s.bpm = s.ny + (2 if s.nc == 3 else 0)
@@ -169,7 +178,7 @@ def parse(data) -> Info:
     while True:
         j = d.find(b"\xff", i)
         if j < 0 or j + 1 >= n:
-            raise Corrupt("no EOI")
+            raise _at(Corrupt("no EOI"), n)
         nx = d[j + 1]
         if nx == 0:
             removed, i = removed + 1, j + 2
@@ -177,25 +186,25 @@ def parse(data) -> Info:
             removed, i = removed + 1, j + 1
         elif 0xD0 <= nx <= 0xD7:
             if s.restart == 0 or nx - 0xD0 != len(cuts) & 7 or len(cuts) + 1 >= s.nseg:
-                raise Corrupt(f"RST{nx - 0xD0} at byte {j}")
+                raise _at(Corrupt(f"RST{nx - 0xD0} at byte {j}"), j)
             cuts.append(j - pos - removed)
             removed, i = removed + 2, j + 2
         else:
             break
     if nx == 0xDC:
-        raise Unsupported("DNL")
+        raise _at(Unsupported("DNL"), j)
     if nx != 0xD9:
-        raise Unsupported("several scans")
+        raise _at(Unsupported("several scans"), j)
     if len(cuts) + 1 != s.nseg:
-        raise Corrupt("restart markers missing")
+        raise _at(Corrupt("restart markers missing"), j)
     s.scan_len = j - pos
     s.segoff = [0] + cuts + [s.scan_len - removed]          # bytes of the unstuffed stream
     if any(b <= a for a, b in zip(s.segoff, s.segoff[1:])):
-        raise Corrupt("an empty segment")
+        raise _at(Corrupt("an empty segment"), pos)
     if s.scan_len >= (1 << 32) - 32:
-        raise Unsupported("a stuffed scan of 2 ** 32 bytes")
+        raise _at(Unsupported("a stuffed scan of 2 ** 32 bytes"), pos)
     if s.segoff[-1] * 8 >= 1 << 31:
-        raise Unsupported("a scan of 2 ** 31 bits")
+        raise _at(Unsupported("a scan of 2 ** 31 bits"), pos)
     s.data = d
     return s
 

@@ -191,9 +191,10 @@ def _entropy_bytes(tokens, code, length):
     return bytes(out)
 
 
-def progressive(zz, g, qts, script) -> bytes:
+def progressive(zz, g, qts, script, table=None) -> bytes:
     """A progressive file of the quantised coefficients ``zz`` ((nblocks, 64), zigzag, MCU-major, DC as values), geometry ``g`` (h, w,
-    nc, hs, vs), quantisation tables ``qts`` (row-major, luma and chroma) and the scans of ``script``."""
+    nc, hs, vs), quantisation tables ``qts`` (row-major, luma and chroma) and the scans of ``script``.  ``table(counts, ac, k)``: the
+    (table spec, slot 0 ... 3) of scan ``k`` from its symbol counts; None: the optimal table in slot 0."""
     out = bytearray(b"\xff\xd8")
     out += DC.segment(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
     for i, q in enumerate(qts[:1 if g.nc == 1 else 2]):
@@ -203,7 +204,7 @@ def progressive(zz, g, qts, script) -> bytes:
         sof += bytes([c + 1, (g.hs << 4 | g.vs) if c == 0 and g.nc == 3 else 0x11, 0 if c == 0 else 1])
     out += DC.segment(0xC2, sof)
     interval = 0
-    for sc in script:
+    for k, sc in enumerate(script):
         if sc["dri"] is not None:
             interval = sc["dri"]
             out += DC.segment(0xDD, struct.pack(">H", interval))
@@ -215,15 +216,16 @@ def progressive(zz, g, qts, script) -> bytes:
                 if t[0] == "s":
                     counts[t[1]] += 1
         code = length = None
+        slot = 0
         if counts.any():
-            spec = OR.optimal_table(counts)
+            spec, slot = (OR.optimal_table(counts), 0) if table is None else table(counts, bool(sc["Ss"]), k)
             code, length = R.code_table(spec)
-            out += DC.segment(0xC4, bytes([0x10 if sc["Ss"] else 0x00]) + bytes(spec[0]) + bytes(spec[1]))
-        out += DC.segment(0xDA, bytes([len(sc["comps"])]) + b"".join(bytes([c + 1, 0]) for c in sc["comps"]) +
+            out += DC.segment(0xC4, bytes([(0x10 if sc["Ss"] else 0x00) | slot]) + bytes(spec[0]) + bytes(spec[1]))
+        out += DC.segment(0xDA, bytes([len(sc["comps"])]) + b"".join(bytes([c + 1, slot << 4 | slot]) for c in sc["comps"]) +
                           bytes([sc["Ss"], sc["Se"], sc["Ah"] << 4 | sc["Al"]]))
-        for k, seg in enumerate(segs):
-            if k:
-                out += bytes([0xFF, 0xD0 + (k - 1) % 8])
+        for i, seg in enumerate(segs):
+            if i:
+                out += bytes([0xFF, 0xD0 + (i - 1) % 8])
             out += _entropy_bytes(seg, code, length)
     return bytes(out + b"\xff\xd9")
 

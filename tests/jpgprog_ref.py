@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from jpgdec_ref import DEFAULT_SUBSEQ_BITS, Corrupt, Huff, Info, Unsupported, _be16, pixels, unstuffed
+from jpgdec_ref import DEFAULT_SUBSEQ_BITS, Corrupt, Huff, Info, Unsupported, _at, _be16, pixels, unstuffed
 from jpg_ref import ZIGZAG
 
 DC_FIRST, DC_REFINE, AC_FIRST, AC_REFINE = 0, 1, 2, 3
@@ -33,7 +33,7 @@ def parse(data) -> Info:
     d = bytes(data)
     n = len(d)
     if n < 4 or d[0] != 0xFF or d[1] != 0xD8:
-        raise Corrupt("no SOI")
+        raise _at(Corrupt("no SOI"), 0)
     s = Info()
     q, dc, ac = [None] * 4, [None] * 4, [None] * 4
     s.q, s.scans, s.data = [None] * 3, [], d
@@ -42,45 +42,45 @@ def parse(data) -> Info:
     pos = 2
     while True:
         if pos + 1 >= n or d[pos] != 0xFF:
-            raise Corrupt("marker expected")
+            raise _at(Corrupt("marker expected"), pos)
         while pos + 1 < n and d[pos + 1] == 0xFF:
             pos += 1
         if pos + 1 >= n:
-            raise Corrupt("file ends in a marker")
+            raise _at(Corrupt("file ends in a marker"), pos)
         m = d[pos + 1]
         pos += 2
         if m == 0x01 or 0xD0 <= m <= 0xD7:
             continue
         if m == 0xD9:
             if not s.scans:
-                raise Corrupt("EOI before the scan")
+                raise _at(Corrupt("EOI before the scan"), pos - 2)
             break
         if m == 0xD8:
-            raise Corrupt("SOI")
+            raise _at(Corrupt("SOI"), pos - 2)
         if pos + 2 > n:
-            raise Corrupt("segment length")
+            raise _at(Corrupt("segment length"), pos)
         ln = _be16(d, pos)
         if ln < 2 or pos + ln > n:
-            raise Corrupt("segment length")
+            raise _at(Corrupt("segment length"), pos)
         body = d[pos + 2:pos + ln]
         if m == 0xC2:
             if frame is not None or len(body) < 6 or len(body) != 6 + 3 * body[5]:
-                raise Corrupt("SOF")
+                raise _at(Corrupt("SOF"), pos)
             if body[0] != 8:
-                raise Unsupported(f"{body[0]}-bit samples")
+                raise _at(Unsupported(f"{body[0]}-bit samples"), pos)
             s.h, s.w, s.nc = _be16(body, 1), _be16(body, 3), body[5]
             if s.h == 0:
-                raise Unsupported("height 0: DNL")
+                raise _at(Unsupported("height 0: DNL"), pos)
             if s.w == 0:
-                raise Corrupt("width 0")
+                raise _at(Corrupt("width 0"), pos)
             if s.nc not in (1, 3):
-                raise Unsupported(f"{s.nc} components")
+                raise _at(Unsupported(f"{s.nc} components"), pos)
             frame = [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(s.nc)]
             if s.nc == 1:
                 s.hs = s.vs = 1
             else:
                 if (frame[1][1], frame[1][2], frame[2][1], frame[2][2]) != (1, 1, 1, 1) or (frame[0][1], frame[0][2]) not in ((1, 1), (2, 1), (2, 2)):
-                    raise Unsupported("sampling factors")
+                    raise _at(Unsupported("sampling factors"), pos)
                 s.hs, s.vs = frame[0][1], frame[0][2]
             s.ny = s.hs * s.vs
             s.bpm = s.ny + (2 if s.nc == 3 else 0)
@@ -93,29 +93,32 @@ def parse(data) -> Info:
             s.cw, s.ch = -(-s.w // s.hs), -(-s.h // s.vs)
             bits = [[-1] * 64 for _ in range(s.nc)]
         elif m in (0xC0, 0xC1):
-            raise Unsupported("a sequential file")
+            raise _at(Unsupported("a sequential file"), pos)
         elif m in (0xC3, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xCB, 0xCC, 0xCD, 0xCE, 0xCF):
-            raise Unsupported("lossless or arithmetic")
+            raise _at(Unsupported("lossless or arithmetic"), pos)
         elif m == 0xC4:
             i = 0
             while i < len(body):
                 if i + 17 > len(body) or (body[i] >> 4) > 1 or (body[i] & 15) > 3:
-                    raise Corrupt("DHT")
+                    raise _at(Corrupt("DHT"), pos)
                 b16 = body[i + 1:i + 17]
                 cnt = sum(b16)
                 if cnt > 256 or i + 17 + cnt > len(body):
-                    raise Corrupt("DHT")
+                    raise _at(Corrupt("DHT"), pos)
                 vals = body[i + 17:i + 17 + cnt]
                 if (body[i] >> 4) == 0 and any(v > 15 for v in vals):
-                    raise Corrupt("DHT: DC category above 15")
-                (ac if body[i] >> 4 else dc)[body[i] & 15] = Huff(b16, vals)
+                    raise _at(Corrupt("DHT: DC category above 15"), pos)
+                try:
+                    (ac if body[i] >> 4 else dc)[body[i] & 15] = Huff(b16, vals)
+                except Corrupt as e:
+                    raise _at(e, pos)
                 i += 17 + cnt
         elif m == 0xDB:
             i = 0
             while i < len(body):
                 pq, tq = body[i] >> 4, body[i] & 15
                 if pq > 1 or tq > 3 or i + 1 + 64 * (pq + 1) > len(body):
-                    raise Corrupt("DQT")
+                    raise _at(Corrupt("DQT"), pos)
                 t = np.zeros(64, np.int64)
                 for k in range(64):
                     t[ZIGZAG[k]] = _be16(body, i + 1 + 2 * k) if pq else body[i + 1 + k]
@@ -123,22 +126,22 @@ def parse(data) -> Info:
                 i += 1 + 64 * (pq + 1)
         elif m == 0xDD:
             if ln != 4:
-                raise Corrupt("DRI")
+                raise _at(Corrupt("DRI"), pos)
             restart = _be16(body, 0)
         elif m == 0xDC:
-            raise Unsupported("DNL")
+            raise _at(Unsupported("DNL"), pos)
         elif m == 0xEE and len(body) >= 12 and body[:5] == b"Adobe":
             adobe = body[11]
         elif m == 0xDA:
             if frame is None or len(body) < 1 or len(body) != 4 + 2 * body[0] or not 1 <= body[0] <= s.nc:
-                raise Corrupt("SOS")
+                raise _at(Corrupt("SOS"), pos)
             sc = Info()
             ns = body[0]
             Ss, Se, Ah, Al = body[-3], body[-2], body[-1] >> 4, body[-1] & 15
             if Ss > 63 or Se > 63 or Se < Ss or (Ss == 0 and Se != 0) or (Ss > 0 and ns != 1) or Al > 13:
-                raise Corrupt("an illegal scan")
+                raise _at(Corrupt("an illegal scan"), pos)
             if Ah != 0 and Ah != Al + 1:
-                raise Corrupt("an illegal scan: a refinement by other than one bit")
+                raise _at(Corrupt("an illegal scan: a refinement by other than one bit"), pos)
             sc.kind = (AC_FIRST if Ss else DC_FIRST) + (1 if Ah else 0)
             sc.Ss, sc.Se, sc.Al, sc.Ah, sc.ni = Ss, Se, Al, Ah, ns == 1
             sc.comps, sc.jk, sc.jdc, sc.jc = [], [], [], []   # per block j of the scan's MCU: place in the file's MCU, DC table, component
@@ -146,25 +149,25 @@ def parse(data) -> Info:
             for i in range(ns):
                 c = [k for k in range(s.nc) if frame[k][0] == body[1 + 2 * i]]
                 if not c:
-                    raise Corrupt("SOS: no such component")
+                    raise _at(Corrupt("SOS: no such component"), pos)
                 c = c[-1]
                 if c <= before:
-                    raise Unsupported("scan components out of order")
+                    raise _at(Unsupported("scan components out of order"), pos)
                 before = c
                 td, ta = body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15
                 if td > 3 or ta > 3 or (sc.kind == DC_FIRST and dc[td] is None) or (sc.kind >= AC_FIRST and ac[ta] is None):
-                    raise Corrupt("a table the scan names is missing")
+                    raise _at(Corrupt("a table the scan names is missing"), pos)
                 if s.q[c] is None:
                     if frame[c][3] > 3 or q[frame[c][3]] is None:
-                        raise Corrupt("a table the scan names is missing")
+                        raise _at(Corrupt("a table the scan names is missing"), pos)
                     s.q[c] = q[frame[c][3]].copy()
                 for k in range(Ss, Se + 1):
                     if Ah == 0 and bits[c][k] != -1:
-                        raise Unsupported("a coefficient's first scan comes twice")
+                        raise _at(Unsupported("a coefficient's first scan comes twice"), pos)
                     if Ah != 0 and bits[c][k] == -1:
-                        raise Corrupt("a refinement of a coefficient whose first scan never came")
+                        raise _at(Corrupt("a refinement of a coefficient whose first scan never came"), pos)
                     if Ah != 0 and bits[c][k] != Ah:
-                        raise Corrupt("a refinement out of step")
+                        raise _at(Corrupt("a refinement out of step"), pos)
                     bits[c][k] = Al
                 sc.comps.append(c)
                 sc.ac = ac[ta]
@@ -187,7 +190,7 @@ def parse(data) -> Info:
             while True:
                 j = d.find(b"\xff", i)
                 if j < 0 or j + 1 >= n:
-                    raise Corrupt("no EOI")
+                    raise _at(Corrupt("no EOI"), n)
                 nx = d[j + 1]
                 if nx == 0:
                     removed, i = removed + 1, j + 2
@@ -195,31 +198,31 @@ def parse(data) -> Info:
                     removed, i = removed + 1, j + 1
                 elif 0xD0 <= nx <= 0xD7:
                     if restart == 0 or nx - 0xD0 != len(cuts) & 7 or len(cuts) + 1 >= sc.nseg:
-                        raise Corrupt(f"RST{nx - 0xD0} at byte {j}")
+                        raise _at(Corrupt(f"RST{nx - 0xD0} at byte {j}"), j)
                     cuts.append(j - pos - removed)
                     removed, i = removed + 2, j + 2
                 else:
                     break
             if nx == 0xDC:
-                raise Unsupported("DNL")
+                raise _at(Unsupported("DNL"), j)
             if len(cuts) + 1 != sc.nseg:
-                raise Corrupt("restart markers missing")
+                raise _at(Corrupt("restart markers missing"), j)
             sc.scan_len = j - pos
             sc.segoff = [0] + cuts + [sc.scan_len - removed]
             if sc.scan_len >= (1 << 32) - 32:
-                raise Unsupported("a stuffed scan of 2 ** 32 bytes")
+                raise _at(Unsupported("a stuffed scan of 2 ** 32 bytes"), pos)
             if sc.segoff[-1] * 8 >= 1 << 31:
-                raise Unsupported("a scan of 2 ** 31 bits")
+                raise _at(Unsupported("a scan of 2 ** 31 bits"), pos)
             if any(b <= a for a, b in zip(sc.segoff, sc.segoff[1:])):
-                raise Corrupt("an empty segment")
+                raise _at(Corrupt("an empty segment"), pos)
             s.scans.append(sc)
             pos = j
             continue
         pos += ln
     if s.nc == 3 and adobe == 0:
-        raise Unsupported("Adobe transform 0: RGB")
+        raise _at(Unsupported("Adobe transform 0: RGB"), pos)
     if any(b != 0 for row in bits for b in row):
-        raise Unsupported("the scans leave coefficients unfinished")
+        raise _at(Unsupported("the scans leave coefficients unfinished"), pos)
     return s
 
 

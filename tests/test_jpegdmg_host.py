@@ -2,8 +2,8 @@
 parse; the restatements against their own plain decoders on every damaged file that is still a legal stream; the product's host
 builds -- tests/host_jpegdec, tests/host_jpegdec_prog, tests/host_jpegdec_batch -- against the restatement in return code, error bit,
 error scan, rounds and pixels with 0 differing, on the lists the GPU half runs and on a longer draw of the same generator; the lossless
-entries' host builds (tests/host_jpegxc, tests/host_jpegxf) on a damaged source against jpgxc_ref / jpgxf_ref; and the forty cases of
-the GPU fuzz slice through the host builds.  A disagreement between ``*_core.hpp`` and the contract shows here first;
+entries' host builds (tests/host_jpegxc, tests/host_jpegxf) on a damaged source against jpgxc_ref / jpgxf_ref; and the cases of
+the GPU fuzz slices (--jpegdmg, --jpegodd) through the host builds.  A disagreement between ``*_core.hpp`` and the contract shows here first;
 tests/test_gpu_jpegdmg.py then holds the kernels to the same verdicts.  The stand-alone sanitizer runs of the five host tests take
 the same files."""
 import ctypes as C
@@ -331,3 +331,24 @@ def test_the_fuzz_slices_cases_on_the_host_builds(emul_seq, emul_prog, product_l
     print("fuzz slice:", seen)
     assert not bad, bad
     assert seen.get("refused", 0) >= 10 and seen.get("decoded", 0) >= 5
+    # the cases of the --jpegodd slice (tests/test_gpu_fuzz_jpegodd.py): legal files of unusual structure and damaged headers
+    import jpgodd_cases as O
+
+    seen, kinds = {}, {}
+    for case in range(O.FUZZ_CASES):
+        rng = np.random.default_rng([O.FUZZ_SEED, case])
+        rng.random()
+        desc, data, prog, S = F.jpegodd_draw(rng)
+        v = O.header_verdict_of(data, S, prog)
+        kinds[" odd legal " in desc] = kinds.get(" odd legal " in desc, 0) + 1
+        seen[v.what] = seen.get(v.what, 0) + 1
+        rc, _ = (TP if prog else TD)._emul_info(emul_prog if prog else emul_seq, data)
+        if rc != {"parsed": 0, "unsupported": 1, "corrupt": 2}[v.what]:
+            bad[case] = (desc, f"parse rc {rc} for {v.what}")
+        elif v.inner is not None:
+            d = (prog_differences(emul_prog, data, S, v.inner) if prog else seq_differences(emul_seq, data, S, v.inner))
+            if d:
+                bad[case] = (desc, d)
+    print("jpegodd slice:", seen, kinds)
+    assert not bad, bad
+    assert kinds.get(True, 0) >= 10 and kinds.get(False, 0) >= 10 and seen.get("corrupt", 0) >= 5

@@ -7,7 +7,7 @@ and destination views (dword-aligned or not), per-unit rotations, apply_lr pairs
 (v1c_remap_lut) on random float32 maps sprinkled with NaN, infinities, 2^15 / 2^26 / 2^31-scale values and ties of the 1/32 grid.
 
     python3 tools/fuzz.py [--seconds 300] [--seed 1] [--big 0.15] [--lut 0.15] [--hot 0.3] [--gen2 0] [--api 0.1] [--auto 0.06] [--fused 0.06] [--log gpurun_out/fuzz.log]
-                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--jpegprog 0] [--jpegxc 0] [--jpegxf 0] [--jpegdmg 0] [--cases N]
+                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--jpegprog 0] [--jpegxc 0] [--jpegxf 0] [--jpegdmg 0] [--jpegodd 0] [--cases N]
 
 --wide P: that share of the cases has uint16 or float32 pixels (k_remap_wide): the chain cases above -- same grammar, views, batches, pairs,
 per-unit rotations, graph replays and the same three masks, counted in the same counters -- and the LUT cases (v1c_remap_lut_ex, nothing left
@@ -32,7 +32,10 @@ against tests/jpgprog_ref.py: pixels, scans and the rounds of every scan.  --jpe
 v1c_jpeg_prog_decode) with a DAMAGED scan -- a file as --jpegdec / --jpegprog draw it, one random damage of tests/jpgdmg_cases.py's kinds (a bit
 flipped, a byte replaced, 1-3 bytes deleted or inserted, two restart segments exchanged, the scan filled) inside the entropy-coded bytes of one
 scan, a random subsequence size -- against the restatement's verdict: the code, the smallest bad bit and its scan, the rounds, and the pixels of
-damage that is still a legal stream (the summary line says how many cases were refused by the last pass, decoded, or left to the parse).  These shares come off the top of the
+damage that is still a legal stream (the summary line says how many cases were refused by the last pass, decoded, or left to the parse).  --jpegodd P: that share goes through the same two entries with a LEGAL file of unusual structure (drawn Huffman code shapes
+and table slots, 16-bit quantisation tables, component ids, segment orders, fill bytes, DRI oddities) or with ONE damage in a marker
+segment of a small supported file (tests/jpgodd_cases.py), against the restatement: the parse's class, then the verdict as for --jpegdmg
+(the summary line says how many were refused as predicted).  These shares come off the top of the
 case draw: with all of them at 0 every earlier seed replays as it ran.
 
 Round 5 added to the grammar: hot shapes of the chains that left the interpreter (planar fisheye -> fisheye, is_latitude_y=False, a
@@ -1313,6 +1316,13 @@ def jpegdmg_case(rng, dev) -> tuple[str, int]:
     DMG["drawn"] += 1
     DMG[want.what if want.what in ("refused", "decoded") else "parse"] += 1
     KINDS["jpegdmg"] = KINDS.get("jpegdmg", 0) + 1
+    return jpegdmg_compare(desc, data, prog, S, want)
+
+
+def jpegdmg_compare(desc, data, prog, S, want) -> tuple[str, int]:
+    """the device decoder's answer for a file against a verdict of jpgdmg_cases.verdict_of"""
+    import jpgdmg_cases as M
+
     h, w = want.pixels.shape[:2] if want.what == "decoded" else (8, 8)
     if want.what == "refused":
         s = (M.P.parse if prog else M.D.parse)(data)
@@ -1326,6 +1336,44 @@ def jpegdmg_case(rng, dev) -> tuple[str, int]:
     if want.what == "decoded" and rc == 0:
         bad += int((px != want.pixels).sum())
     return f"{desc} restatement: {want.what} bit={want.bit} scan={want.scan} rounds={want.rounds}; device: rc={rc} bit={bit} scan={scan} rounds={rounds}", bad
+
+
+ODD = {"drawn": 0, "legal": 0, "damage": 0, "refused": 0}  # jpegodd cases; refused: by the parse or the last pass, as the restatement predicts
+
+
+def jpegodd_draw(rng) -> tuple[str, bytes, bool, int]:
+    """(description, file, whether it is progressive, subsequence size) of a --jpegodd case: one legal file of unusual structure --
+    drawn Huffman code shapes and table slots, quantisation slots and widths, component ids, segment orders, fill bytes, DRI oddities
+    (tests/jpgodd_cases.py: random_legal, one file in four progressive) -- or one small supported file with one damage in a marker segment (random_damage)"""
+    import jpgodd_cases as O
+
+    if rng.random() < 0.5:
+        desc, data, prog = O.random_legal(rng)
+    else:
+        desc, data, prog = O.random_damage(rng)
+    S = int(rng.choice([256, 256, 288, 512, 1024]))
+    return f"JPEGODD {'progressive' if prog else 'sequential'} {desc} subseq_bits={S}", data, prog, S
+
+
+def jpegodd_case(rng, dev) -> tuple[str, int]:
+    """an odd legal file or a damaged header through the device decoders against the restatement (jpgodd_cases.header_verdict_of):
+    the parse's class and the byte it stops at, and for what the parse takes the code, the bad bit and its scan, the rounds and the pixels"""
+    import jpgdmg_cases as M
+    import jpgodd_cases as O
+
+    desc, data, prog, S = jpegodd_draw(rng)
+    v = O.header_verdict_of(data, S, prog)
+    want = v.inner if v.inner is not None else M.Verdict("unsupported" if v.what == "unsupported" else "parse")
+    ODD["drawn"] += 1
+    ODD["legal" if " odd legal " in desc else "damage"] += 1
+    ODD["refused"] += want.what != "decoded"
+    KINDS["jpegodd"] = KINDS.get("jpegodd", 0) + 1
+    if v.inner is not None:
+        return jpegdmg_compare(desc, data, prog, S, want)
+    # refused by the parse: the code, and the byte the parse stopped at in the report's error_pos
+    rc, pos, _, _, _ = jpegdmg_device(data, prog, S, 8, 8)
+    bad = (0 if rc == (-2 if v.what == "unsupported" else -5) else 1) + (0 if pos == v.pos else 1)
+    return f"{desc} restatement's parse: {v.what} at byte {v.pos} ({v.why}); device entry: rc={rc} error_pos={pos}", bad
 
 
 FEAT = {"drawn": 0, "refused": 0}  # feat cases drawn / of them refused by v1c_feat_detect as feat_ref.refusal predicts (not counted)
@@ -1498,6 +1546,7 @@ def main() -> int:
     ap.add_argument("--jpegxc", type=float, default=0.0, help="share of cases through the lossless JPEG transcoder (transcode_regions: crops, splits, swaps) against jpgxc_ref.transcode")
     ap.add_argument("--jpegxf", type=float, default=0.0, help="share of cases through the lossless JPEG composer (compose_regions: joins, rotations, flips of up to four files) against jpgxf_ref.compose")
     ap.add_argument("--jpegdmg", type=float, default=0.0, help="share of cases through the device JPEG decoders with one random damage inside a scan, against the verdict of tests/jpgdmg_cases.py")
+    ap.add_argument("--jpegodd", type=float, default=0.0, help="share of cases through the device JPEG decoders with a legal file of unusual structure or one damaged header, against tests/jpgodd_cases.py")
     ap.add_argument("--cases", type=int, default=None, help="stop after this many cases (before --seconds runs out)")
     ap.add_argument("--feat", type=float, default=0.0, help="share of cases through the feature pipeline (features.detect / features.match) against tests/feat_ref.py")
     ap.add_argument("--only", type=int, default=None, help="run only this case number (reproduce)")
@@ -1532,10 +1581,13 @@ def main() -> int:
             r_kind = rng.random()
             wide_chain = False
             counted = True
-            rest0 = 1.0 - a.jpegdmg
+            rest00 = 1.0 - a.jpegodd
+            rest0 = rest00 - a.jpegdmg
             rest = rest0 - a.jpegxf
             top = rest - a.jpegxc - a.jpegprog - a.jpegopt - a.jpegbatch - a.jpegdec
-            if r_kind >= rest0:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+            if r_kind >= rest00:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+                desc, bad = jpegodd_case(rng, dev)
+            elif r_kind >= rest0:
                 desc, bad = jpegdmg_case(rng, dev)
             elif r_kind >= rest:
                 desc, bad = jpegxf_case(rng, dev)
@@ -1599,7 +1651,9 @@ def main() -> int:
         + (f"; feat cases: {FEAT['drawn']} drawn, {FEAT['refused']} of them refused as predicted and not counted" if FEAT["drawn"] else "")
         + (f"; jpegxf cases: {XF['drawn']} drawn, {XF['refused']} of them refused by both sides alike" if XF["drawn"] else "")
         + (f"; jpegdmg cases: {DMG['drawn']} drawn, {DMG['refused']} refused by the last pass, {DMG['decoded']} decoded, {DMG['parse']} left to the parse"
-           if DMG["drawn"] else ""))
+           if DMG["drawn"] else "")
+        + (f"; jpegodd cases: {ODD['drawn']} drawn, {ODD['legal']} legal files and {ODD['damage']} damaged headers, {ODD['refused']} of them refused as predicted"
+           if ODD["drawn"] else ""))
     say("kernel families of the chain cases' launch groups: " + ", ".join(f"{k} x{v}" for k, v in sorted(KINDS.items())))
     return 1 if n_bad else 0
 
