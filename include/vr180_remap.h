@@ -365,6 +365,49 @@ int v1c_feat_match(int device, void* stream, const uint8_t* desc_a, int n_a, con
  * Host-only; `out` is a HOST buffer.                                                                                            */
 int v1c_feat_pattern(int8_t* out);
 
+/* ---- the image circle from its rim (INTEGRATION.md section 11 states the contract; tests/circle_ref.py restates it) ---------------
+ * A pixel is LIT when the sum of its channels is >= threshold * cn (the integer complement of get_radius's mean < threshold, alpha
+ * included).  RIM POINTS: from each end of every row, then of every column, the first pixel of the first run of at least `run` lit
+ * pixels; a point on the frame's own first / last column (row, for columns) is dropped.  FIT: Kasa's algebraic circle from the int64
+ * moment sums of the points (coordinates relative to (w / 2, h / 2)), solved in float64, then `rounds` refits, round k over the points
+ * whose distance from the centre of the fit before it lies within tol16[k] / 16 px of its radius -- centre and radius rounded to
+ * 1/16 px (half up), the comparison made on the squares in int64.  The result is a pure function of the pixels and the parameters.
+ * RESULT, eight doubles: cx, cy, r (source pixels, r > 0), status, n_rim, n_used, rms, 0.  status: 0, or 1 (fewer than min_points
+ * points in a fit), 2 (singular system), 3 (r <= 0, r > 4 max(h, w), or a centre further than 8 max(h, w) from the frame's); then
+ * cx = cy = r = rms = 0.  n_used: the points of the last fit made; rms: sqrt(mean((floor(d16) - r16)^2)) / 16 over them, d16 the
+ * distance from the final centre in 1/16 px.  An all-black or all-lit image ends in status 1, not in an error.                  */
+typedef struct v1c_circle_params {
+    int32_t threshold;      /* 0..65535 [10]                                                                                     */
+    int32_t run;            /* 1..64 [4]: isolated lit pixels shorter than this are no rim                                       */
+    int32_t rounds;         /* trimmed refits, 0..8 [4]                                                                          */
+    int32_t min_points;     /* 3..2^20 [8]                                                                                       */
+    int32_t tol16[8];       /* tolerance of round k in 1/16 px, 1..2^20 [128, 48, 24, 24]                                        */
+} v1c_circle_params;
+
+typedef struct v1c_circle_point {
+    int32_t x, y;           /* source pixel                                                                                      */
+    int32_t selected;       /* 1: in the last selection made                                                                     */
+} v1c_circle_point;
+
+/* Bytes of device memory a fit of an (h, w) image needs as its workspace: 2 (h + w) point slots, their flags, the result of the
+ * synchronous form and one record per column and band of 64 rows.  Host-only.  0 for sizes outside 1..32768.                    */
+uint64_t v1c_fit_circle_workspace(int h, int w);
+
+/* Fits the circle of the device image img ((h, w, cn), cn 1 / 3 / 4, depth V1C_DEPTH_8U or _16U, row pitch in BYTES) on `stream`:
+ * four launches, no allocation, no copy, no synchronisation -- it can be captured into a graph.  `workspace`: device memory of
+ * v1c_fit_circle_workspace(h, w) bytes, 4-byte aligned, the caller's, in use until the work has run (one per call in flight);
+ * out_dev8: eight doubles on the device.  params NULL: the defaults.  V1C_E_INVALID before any device call for NULL pointers, cn,
+ * depth, sizes, pitch below a row's bytes, an odd pointer or pitch of a 16-bit image, alignment, parameters out of range.       */
+int v1c_fit_circle_async(int device, void* stream, const void* img, int h, int w, int64_t pitch, int cn, int depth,
+                         const v1c_circle_params* params, void* workspace, double* out_dev8);
+
+/* The same, SYNCHRONISES the stream once and leaves the eight doubles in out_host8 (HOST).  points_out (HOST, may be NULL): the rim
+ * points in order -- by row (left, right), then by column (top, bottom) -- at most `capacity`, their number in *n_points_out
+ * (V1C_E_INVALID after the fact when there are more; 2 (h + w) always suffices).  V1C_E_UNSUPPORTED while `stream` is captured.   */
+int v1c_fit_circle(int device, void* stream, const void* img, int h, int w, int64_t pitch, int cn, int depth,
+                   const v1c_circle_params* params, void* workspace, double* out_host8, v1c_circle_point* points_out,
+                   int32_t capacity, int32_t* n_points_out);
+
 /* ---- PNG encoding of a device image (INTEGRATION.md section 6 states the stream; tests/png_ref.py restates it) ------------------
  * The image's filtered scanlines, cut into bands of band_rows rows, every band deflated from an empty window as ONE dynamic Huffman
  * block of literals and distance-1 matches (zlib's Z_RLE class) closed by an empty stored block, or as stored blocks where that is

@@ -7,7 +7,7 @@ and destination views (dword-aligned or not), per-unit rotations, apply_lr pairs
 (v1c_remap_lut) on random float32 maps sprinkled with NaN, infinities, 2^15 / 2^26 / 2^31-scale values and ties of the 1/32 grid.
 
     python3 tools/fuzz.py [--seconds 300] [--seed 1] [--big 0.15] [--lut 0.15] [--hot 0.3] [--gen2 0] [--api 0.1] [--auto 0.06] [--fused 0.06] [--log gpurun_out/fuzz.log]
-                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--jpegprog 0] [--jpegxc 0] [--jpegxf 0] [--jpegdmg 0] [--jpegodd 0] [--cases N]
+                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--jpegprog 0] [--jpegxc 0] [--jpegxf 0] [--jpegdmg 0] [--jpegodd 0] [--circle 0] [--cases N]
 
 --wide P: that share of the cases has uint16 or float32 pixels (k_remap_wide): the chain cases above -- same grammar, views, batches, pairs,
 per-unit rotations, graph replays and the same three masks, counted in the same counters -- and the LUT cases (v1c_remap_lut_ex, nothing left
@@ -35,8 +35,11 @@ scan, a random subsequence size -- against the restatement's verdict: the code, 
 damage that is still a legal stream (the summary line says how many cases were refused by the last pass, decoded, or left to the parse).  --jpegodd P: that share goes through the same two entries with a LEGAL file of unusual structure (drawn Huffman code shapes
 and table slots, 16-bit quantisation tables, component ids, segment orders, fill bytes, DRI oddities) or with ONE damage in a marker
 segment of a small supported file (tests/jpgodd_cases.py), against the restatement: the parse's class, then the verdict as for --jpegdmg
-(the summary line says how many were refused as predicted).  These shares come off the top of the
-case draw: with all of them at 0 every earlier seed replays as it ran.
+(the summary line says how many were refused as predicted).  --circle P: that share goes through the image-circle fit
+(v1c_fit_circle: random discs, clips, wedges, noise, pixel types, channel counts, views and parameters) against tests/circle_ref.py --
+rim points, selection flags and counts equal, floats within 1e-9 px -- and, for a part of them, through apply() / apply_lr_tensors()
+with random off-centre center= values against oracle.remap of the host NumPy chain's map with those centres.  These shares come off
+the top of the case draw: with all of them at 0 every earlier seed replays as it ran.
 
 Round 5 added to the grammar: hot shapes of the chains that left the interpreter (planar fisheye -> fisheye, is_latitude_y=False, a
 rotation behind radial stages), outputs of 64 ... 416 px, launches recorded into a graph and replayed, radius='auto' with the radius on
@@ -1381,6 +1384,97 @@ FEAT_IMAGES = ["disc", "noise", "low", "scene", "sphere", "flat"]
 FEAT_RATIOS = [(3, 4), (1, 1), (1, 2), (0, 1)]
 
 
+def circle_image(rng) -> tuple[np.ndarray, str]:
+    """an (H, W, C) uint8 / uint16 frame: a disc (often clipped, sometimes with a dark wedge), speckle, hot pixels, or nothing"""
+    import circle_cases as CC
+
+    h, w = (int(rng.integers(1, 400)), int(rng.integers(1, 400))) if rng.random() < 0.85 else (int(rng.integers(400, 1600)), int(rng.integers(400, 1600)))
+    cn = int(rng.choice([1, 3, 4]))
+    dtype = np.uint16 if rng.random() < 0.3 else np.uint8
+    kind = str(rng.choice(["disc", "disc", "clipped", "wedge", "speckle", "hot", "black", "lit"]))
+    top = int(np.iinfo(dtype).max)
+    cx, cy = w * rng.uniform(0.3, 0.7), h * rng.uniform(0.3, 0.7)
+    r = min(h, w) * (rng.uniform(0.2, 0.45) if kind != "clipped" else rng.uniform(0.45, 0.8))
+    a = CC.disc(h, w, cx, cy, r, cn=cn, dtype=dtype, value=int(rng.integers(top // 8, top + 1)), aa=bool(rng.random() < 0.7))
+    if kind == "wedge":
+        y0, x0 = int(rng.integers(0, h)), int(rng.integers(0, w))
+        a[y0:y0 + int(rng.integers(1, h // 3 + 2)), x0:x0 + int(rng.integers(1, w // 3 + 2))] = 0
+    elif kind == "speckle":
+        a[rng.random((h, w)) < rng.uniform(0.05, 0.6)] = top // 3
+    elif kind == "hot":
+        for _ in range(int(rng.integers(1, 60))):
+            a[int(rng.integers(0, h)), int(rng.integers(0, w))] = top
+    elif kind == "black":
+        a[:] = 0
+    elif kind == "lit":
+        a[:] = top
+    return a, f"{kind} {h}x{w}x{cn} {np.dtype(dtype).name} centre ({cx:.2f}, {cy:.2f}) r {r:.2f}"
+
+
+def circle_case(rng, dev) -> tuple[str, int]:
+    """v1c_fit_circle against tests/circle_ref.py; then, for 8-bit three-channel frames, a remap with random off-centre centres"""
+    import circle_ref as CR
+    from vr180_convert_amd import circle, remapper
+
+    CIRCLE["drawn"] += 1
+    if rng.random() < 0.3:
+        return circle_remap_case(rng, dev)
+    a, desc = circle_image(rng)
+    h, w, cn = a.shape
+    kw: dict = {}
+    if rng.random() < 0.4:
+        kw = dict(threshold=int(rng.choice([0, 1, 10, 40, 255, 65535])), run=int(rng.choice([1, 2, 4, 9, 64])),
+                  min_points=int(rng.choice([3, 8, 50])), tol16=[int(v) for v in rng.integers(1, 300, int(rng.integers(0, 9)))])
+    view = str(rng.choice(["contiguous", "pitched", "odd"]))
+    if view == "contiguous":
+        t = torch.from_numpy(a).to(dev)
+    else:  # a slice of a wider (and, for "odd", one row and one column shifted) frame: pitched rows, an odd element offset
+        pad = int(rng.integers(1, 40))
+        base = np.zeros((h + 1, w + pad + 1, cn), a.dtype)
+        oy, ox = (1, 1) if view == "odd" else (0, 0)
+        base[oy:oy + h, ox:ox + w] = a
+        t = torch.from_numpy(base).to(dev)[oy:oy + h, ox:ox + w]
+    desc = f"circle {desc} view {view} {kw}"
+    out, rim = circle.fit_circle_raw(t, points=True, **kw)
+    wout, wrim = CR.fit(a, **kw)
+    if rim.shape != wrim.shape:
+        return desc + f" points {len(rim)} != {len(wrim)}", max(1, abs(len(rim) - len(wrim)))
+    bad = int((rim != wrim).any(axis=1).sum()) + int((out[3:6] != wout[3:6]).sum())
+    if not bad and np.abs(out - wout).max() > 1e-9:
+        return desc + f" floats {out} != {wout}", 1
+    return desc, bad
+
+
+def circle_remap_case(rng, dev) -> tuple[str, int]:
+    h, w = int(rng.integers(24, 700)), int(rng.integers(24, 700))
+    wo, ho = int(rng.integers(8, 600)), int(rng.integers(8, 600))
+    interp = int(rng.choice([0, 1, 2, 4]))
+    r = float(rng.uniform(0.2, 0.6) * min(h, w))
+    cs = [(float(w / 2 + rng.uniform(-0.3, 0.3) * w), float(h / 2 + rng.uniform(-0.3, 0.3) * h)) for _ in range(2)]
+    if rng.random() < 0.3:
+        cs = [tuple(np.round(np.array(c) * 4) / 4) for c in cs]
+    srcs = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for _ in range(2)]
+    t = V.EquirectangularEncoder() * V.FisheyeDecoder("equidistant")
+    form = str(rng.choice(["apply one", "apply each", "lr one", "lr each"]))
+    per = cs if form.endswith("each") else [cs[0], cs[0]]
+    from vr180_convert_amd import remapper
+
+    if form.startswith("apply"):
+        got = V.apply(t, in_paths=srcs, radius=r, center=cs if form.endswith("each") else cs[0], size_output=(wo, ho), interpolation=interp, device=dev)
+    else:
+        sbs = V.apply_lr_tensors(t, torch.from_numpy(srcs[0]).to(dev), torch.from_numpy(srcs[1]).to(dev), radius=r,
+                                 center=tuple(cs) if form.endswith("each") else cs[0], size_output=(wo, ho), interpolation=interp).cpu().numpy()
+        got = [sbs[:, :wo], sbs[:, wo:]]
+    bad = 0
+    for g, s_, c in zip(got, srcs, per):
+        xm, ym = remapper._host_map(t, radius=r, size_input=(h, w), size_output=(wo, ho), center=c)
+        bad += int(neq(np.asarray(g), O.remap(s_, xm, ym, interp)).sum())
+    return f"circle remap {form} {h}x{w} -> {wo}x{ho} interp {interp} radius {r!r} centres {cs} kinds {remapper.last_launch_kinds()}", bad
+
+
+CIRCLE = {"drawn": 0}
+
+
 def feat_draw(rng) -> dict:
     """the draws of feat_case's detect half that decide whether v1c_feat_detect refuses the case: no image, no device (tests/test_feat_host.py
     runs feat_ref.refusal over thousands of them).  Nine in ten sizes are drawn so that the working image reaches 34 pixels, nine in ten
@@ -1547,6 +1641,7 @@ def main() -> int:
     ap.add_argument("--jpegxf", type=float, default=0.0, help="share of cases through the lossless JPEG composer (compose_regions: joins, rotations, flips of up to four files) against jpgxf_ref.compose")
     ap.add_argument("--jpegdmg", type=float, default=0.0, help="share of cases through the device JPEG decoders with one random damage inside a scan, against the verdict of tests/jpgdmg_cases.py")
     ap.add_argument("--jpegodd", type=float, default=0.0, help="share of cases through the device JPEG decoders with a legal file of unusual structure or one damaged header, against tests/jpgodd_cases.py")
+    ap.add_argument("--circle", type=float, default=0.0, help="share of cases through the image-circle fit (v1c_fit_circle) against circle_ref.fit, a part of them remaps with random off-centre center= against the oracle")
     ap.add_argument("--cases", type=int, default=None, help="stop after this many cases (before --seconds runs out)")
     ap.add_argument("--feat", type=float, default=0.0, help="share of cases through the feature pipeline (features.detect / features.match) against tests/feat_ref.py")
     ap.add_argument("--only", type=int, default=None, help="run only this case number (reproduce)")
@@ -1581,11 +1676,14 @@ def main() -> int:
             r_kind = rng.random()
             wide_chain = False
             counted = True
-            rest00 = 1.0 - a.jpegodd
+            rest000 = 1.0 - a.circle
+            rest00 = rest000 - a.jpegodd
             rest0 = rest00 - a.jpegdmg
             rest = rest0 - a.jpegxf
             top = rest - a.jpegxc - a.jpegprog - a.jpegopt - a.jpegbatch - a.jpegdec
-            if r_kind >= rest00:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+            if r_kind >= rest000:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+                desc, bad = circle_case(rng, dev)
+            elif r_kind >= rest00:
                 desc, bad = jpegodd_case(rng, dev)
             elif r_kind >= rest0:
                 desc, bad = jpegdmg_case(rng, dev)
@@ -1653,7 +1751,8 @@ def main() -> int:
         + (f"; jpegdmg cases: {DMG['drawn']} drawn, {DMG['refused']} refused by the last pass, {DMG['decoded']} decoded, {DMG['parse']} left to the parse"
            if DMG["drawn"] else "")
         + (f"; jpegodd cases: {ODD['drawn']} drawn, {ODD['legal']} legal files and {ODD['damage']} damaged headers, {ODD['refused']} of them refused as predicted"
-           if ODD["drawn"] else ""))
+           if ODD["drawn"] else "")
+        + (f"; circle cases: {CIRCLE['drawn']} drawn" if CIRCLE["drawn"] else ""))
     say("kernel families of the chain cases' launch groups: " + ", ".join(f"{k} x{v}" for k, v in sorted(KINDS.items())))
     return 1 if n_bad else 0
 

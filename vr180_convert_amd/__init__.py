@@ -27,6 +27,7 @@ from .jpeg_transcode_device import split_sbs_jpeg, swap_sbs_jpeg, transcode_jpeg
 from .jpeg_compose_device import (compose_regions, join_sbs_jpeg, normalize_orientation_jpeg, sbs_from_vr180_photo,
                                   transform_jpeg)
 from .sharding import remap_sharded
+from .circle import Circle, fit_circle, fit_circle_tensor
 
 __all__ = [
     "TransformerBase",
@@ -82,4 +83,8 @@ __all__ = [
     "join_sbs_jpeg",
     "sbs_from_vr180_photo",
     "normalize_orientation_jpeg",
+    # centre and radius of the image circle from its rim, fitted on the device (center="auto", radius="fit")
+    "fit_circle",
+    "fit_circle_tensor",
+    "Circle",
 ]

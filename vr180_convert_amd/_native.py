@@ -30,6 +30,7 @@ SYMBOLS = [
     "v1c_jpeg_prog_info", "v1c_jpeg_prog_decode",
     "v1c_jpeg_transcode_bound", "v1c_jpeg_transcode_check", "v1c_jpeg_header_xc", "v1c_jpeg_transcode",
     "v1c_jpeg_compose_bound", "v1c_jpeg_compose_check", "v1c_jpeg_header_xf", "v1c_jpeg_compose",
+    "v1c_fit_circle_workspace", "v1c_fit_circle_async", "v1c_fit_circle",
 ]
 
 
@@ -139,6 +140,13 @@ def lib() -> C.CDLL:
         L.v1c_jpeg_header_xf.argtypes = [C.c_char_p, C.c_uint64, i32, i32, i32, i32, vp, C.c_uint32, vp, C.c_uint64]
         L.v1c_jpeg_header_xf.restype = i64
         L.v1c_jpeg_compose.argtypes = [i32, vp, i32, vp, i32, vp, C.c_uint32, vp]
+    except AttributeError:  # (an older build behind V1C_LIB)
+        pass
+    try:
+        L.v1c_fit_circle_workspace.argtypes = [i32, i32]
+        L.v1c_fit_circle_workspace.restype = C.c_uint64
+        L.v1c_fit_circle_async.argtypes = [i32, vp, vp, i32, i32, i64, i32, i32, vp, vp, vp]
+        L.v1c_fit_circle.argtypes = [i32, vp, vp, i32, i32, i64, i32, i32, vp, vp, vp, vp, i32, vp]
     except AttributeError:  # (an older build behind V1C_LIB)
         pass
     L.v1c_plan_run.argtypes = [vp, vp, C.POINTER(_abi.Unit), i32]

@@ -91,30 +91,40 @@ def rotation_match_robust(points_to_be_rotated: np.ndarray, points: np.ndarray, 
 
 
 def match_lr(decoder: TransformerBase | tuple[TransformerBase, TransformerBase], points_l: Sequence[tuple[float, float]],
-             points_r: Sequence[tuple[float, float]], in_paths: Sequence[Any], *, radius: float | str = "auto") -> tuple[np.ndarray, np.ndarray]:
+             points_r: Sequence[tuple[float, float]], in_paths: Sequence[Any], *, radius: float | str = "auto",
+             center: Any = None) -> tuple[np.ndarray, np.ndarray]:
     """Matched pixel positions of the two eyes -> unit rays, the arguments of ``rotation_match`` /
     ``rotation_match_robust`` (reference remapper.py:251-321): the points go back through
     ``(decoder * DenormalizeTransformer((r, r), (W // 2, H // 2))).inverse_transform`` as float32
     coordinates and through ``equidistant_to_3d``.  ``in_paths``: the two images (paths or arrays);
-    only their shape (centre) and, for ``radius="auto"`` / ``"max"``, their pixels are used."""
+    only their shape (centre) and, for ``radius="auto"`` / ``"max"`` / ``"fit"``, their pixels are used.
+    ``center``: the centres the remap will use -- ``None`` (the frame's), ``(cx, cy)`` for both eyes, one per eye, or ``"auto"`` (each
+    image's fitted centre, rounded as the remap rounds it): points sent back through other centres than the remap's give a
+    calibration that does not fit its result."""
     from . import _io
-    from .remapper import get_radius_smart
+    from .remapper import fit_centers, fit_circles, get_radius_smart, per_unit_centers
 
     if len(points_l) != len(points_r):
         raise ValueError("The number of points must be the same.")
     images = [_io.imread(p) if isinstance(p, (str, Path)) else p for p in in_paths]
-    center = (images[0].shape[1] // 2, images[0].shape[0] // 2)
-    radius_ = get_radius_smart(radius, images)
+    fits = fit_circles(images) if isinstance(center, str) or (isinstance(radius, str) and radius == "fit") else None
+    if isinstance(center, str):
+        center = fit_centers(center, images, fits=fits)
+    centers = per_unit_centers(center, 2) or [None, None]
+    centers = [(images[0].shape[1] // 2, images[0].shape[0] // 2) if c is None else c for c in centers]
+    radius_ = get_radius_smart(radius, images) if fits is None else get_radius_smart(radius, images, fits=fits)
 
-    def rays(dec: TransformerBase, pts: Any) -> np.ndarray:
+    def rays(dec: TransformerBase, pts: Any, c: Any) -> np.ndarray:
         pts_ = np.array(pts)
         x, y = pts_[:, 0].astype(np.float32), pts_[:, 1].astype(np.float32)
-        x, y = (dec * DenormalizeTransformer(scale=(radius_, radius_), center=center)).inverse_transform(x, y)
+        x, y = (dec * DenormalizeTransformer(scale=(radius_, radius_), center=c)).inverse_transform(x, y)
         return equidistant_to_3d(x, y)
 
     if isinstance(decoder, tuple):
-        return rays(decoder[0], points_l), rays(decoder[1], points_r)
-    v = rays(decoder, np.concatenate([points_l, points_r], axis=0))
+        return rays(decoder[0], points_l, centers[0]), rays(decoder[1], points_r, centers[1])
+    if centers[0] != centers[1]:
+        return rays(decoder, points_l, centers[0]), rays(decoder, points_r, centers[1])
+    v = rays(decoder, np.concatenate([points_l, points_r], axis=0), centers[0])
     return v[: len(points_l)], v[len(points_l):]
 
 

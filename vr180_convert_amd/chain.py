@@ -535,11 +535,26 @@ class Euclidean3DRotator(Euclidean3DTransformer):
     lower_inverse = lower
 
 
+def denormalize_center(size_input: tuple[int, int], center: Any = None) -> tuple:
+    """The centre of the ``DenormalizeTransformer`` get_map() appends: ``(W_in // 2, H_in // 2)`` -- the reference's, two ints -- for
+    ``center=None``, else the given ``(cx, cy)`` in source pixels as two floats (an image circle off the frame's centre: circle.py)."""
+    if center is None:
+        return (size_input[1] // 2, size_input[0] // 2)
+    if isinstance(center, str):
+        raise ValueError(f"center={center!r} needs the images: resolve it first (remap_tensors, apply, apply_lr take center='auto')")
+    cx, cy = center
+    cx, cy = float(cx), float(cy)
+    if not (np.isfinite(cx) and np.isfinite(cy)):
+        raise ValueError("center must be two finite numbers")
+    return (cx, cy)
+
+
 def lower_for_get_map(transformer: TransformerBase, *, radius: float, size_input: tuple[int, int],
-                      size_output: tuple[int, int], row_band: tuple[int, int] | None = None) -> _abi.Chain:
+                      size_output: tuple[int, int], row_band: tuple[int, int] | None = None, center: Any = None) -> _abi.Chain:
     """The chain get_map() evaluates (remapper.py:50-57):
     ``NormalizeTransformer() * transformer * DenormalizeTransformer((r, r), (W_in // 2, H_in // 2))``
     lowered for an output grid of ``size_output`` = (W, H); ``size_input`` = (H_in, W_in).
+    ``center`` = (cx, cy): the image circle's centre in source pixels instead of ``(W_in // 2, H_in // 2)``.
     ``row_band`` = (r0, r1): the chain of output rows r0 .. r1 - 1 only, as a grid of its own (one eye's rows split
     over several GPUs): the same Normalize with its centre moved up by r0 rows -- row j' of the band
     gets ((j' + r0) - H / 2) / s * 2 from the exactly representable difference (j' - (H / 2 - r0)), i.e. the very
@@ -556,7 +571,7 @@ def lower_for_get_map(transformer: TransformerBase, *, radius: float, size_input
     full = (
         norm
         * transformer
-        * DenormalizeTransformer(scale=(radius, radius), center=(size_input[1] // 2, size_input[0] // 2))
+        * DenormalizeTransformer(scale=(radius, radius), center=denormalize_center(size_input, center))
     )
     ops = full.lower(out_shape)
     if row_band is not None and ops and ops[0].opcode == _abi.OP_NORMALIZE and ops[0].nparam == 3:

@@ -71,7 +71,25 @@ def parse_size(size: str) -> tuple[int, int]:
 
 
 def parse_radius(radius: str) -> Any:
-    return radius if radius in ("auto", "max") else float(radius)
+    return radius if radius in ("auto", "max", "fit") else float(radius)
+
+
+def parse_center(center: str, *, pair: bool = True, swap: bool = False) -> Any:
+    """``--center``: '' -> None (the frame's centre), 'auto' -> 'auto' (fitted per image), 'X,Y' -> (x, y), and for a pair of eyes
+    'LX,LY;RX,RY' -> ((lx, ly), (rx, ry)), which ``swap`` exchanges with the eyes"""
+    if center == "":
+        return None
+    if center == "auto":
+        return "auto"
+    try:
+        pts = [tuple(float(v) for v in part.split(",")) for part in center.split(";")]
+        if not all(len(q) == 2 for q in pts) or len(pts) not in ((1, 2) if pair else (1,)):
+            raise ValueError(center)
+    except ValueError as e:
+        raise typer.BadParameter(f"--center {center}: expected 'auto', 'X,Y'" + (" or 'LX,LY;RX,RY'" if pair else "")) from e
+    if len(pts) == 1:
+        return pts[0]
+    return (pts[1], pts[0]) if swap else (pts[0], pts[1])
 
 
 def closest_in_time(directory: Path, anchor: Path, offset_s: float) -> Path:
@@ -126,12 +144,14 @@ def _option_number(automatch: str, prefix: str, pattern: str, default: float) ->
     return float(m.group(1)) if m and m.group(1) else default
 
 
-def calibrated_pair(transformer: Any, automatch: str, left: Any, right: Any, radius: Any, match_image_path: Optional[Path] = None) -> tuple[Any, Any]:
+def calibrated_pair(transformer: Any, automatch: str, left: Any, right: Any, radius: Any, match_image_path: Optional[Path] = None,
+                    center: Any = None) -> tuple[Any, Any]:
     """``--automatch``: estimate the rotation between the eyes from matched points and give each eye half of it
     (cli.py:234-319): (left chain, right chain).  The points come from the option itself (``"xl,yl;xr,yr;..."``: even entries the
     left eye, odd entries the right; plain least-squares fit ``rotation_match``), from clicks (``gui[n]``: n pairs, default 2) or from
     AKAZE feature matching (``fm[scale]``: outlier-ridden, hence ``rotation_match_robust``; ``match_image_path`` = where
-    ``--savematch`` wants 100 of the surviving matches drawn)."""
+    ``--savematch`` wants 100 of the surviving matches drawn).  ``center``: the centres the remap will use (``--center``): the points go
+    back through the same ones (``match_lr``)."""
     head, tail = split_at_first_encoder(transformer)
     matched = None
     if automatch.startswith("devfm"):
@@ -164,7 +184,7 @@ def calibrated_pair(transformer: Any, automatch: str, left: Any, right: Any, rad
     else:
         flat = [(int(c.split(",")[0]), int(c.split(",")[1])) for c in automatch.split(";")]
         points_l, points_r = flat[::2], flat[1::2]  # even entries: left eye, odd entries: right eye
-    vl, vr = match_lr(tail, points_l, points_r, in_paths=[left, right], radius=radius)
+    vl, vr = match_lr(tail, points_l, points_r, in_paths=[left, right], radius=radius, **({} if center is None else {"center": center}))
     if matched is not None:
         q, discarded = rotation_match_robust(vl, vr)
         if match_image_path is not None and automatch.startswith("fm"):
@@ -201,7 +221,9 @@ def lr(
     interpolation: Annotated[str, typer.Option(help="Interpolation method (cv2 name)")] = "inter_lanczos4",
     border_mode: Annotated[str, typer.Option(help="Border mode (cv2 name)")] = "border_constant",
     border_value: int = 0,
-    radius: Annotated[str, typer.Option(help="Radius of the fisheye image: a number, 'auto' or 'max'")] = "auto",
+    radius: Annotated[str, typer.Option(help="Radius of the fisheye image: a number, 'auto', 'max' or 'fit' (the fitted image circle's)")] = "auto",
+    center: Annotated[str, typer.Option(help="Centre of the image circles in source pixels: 'auto' (fitted per eye), 'X,Y' or "
+                                             "'LX,LY;RX,RY' (each in its own eye's coordinates); default: the frame's centre")] = "",
     merge: Annotated[bool, typer.Option("-m", "--merge", "--anaglyph", help="Export as an anaglyph")] = False,
     autosearch_timestamp_calib_r_earlier_l: Annotated[float, typer.Option(
         "--autosearch-timestamp-calib-r-earlier-l", "-ac",
@@ -244,6 +266,7 @@ def lr(
     interp = _flag(interpolation, _INTERPOLATIONS, "inter_", "interpolation")
     border = _flag(border_mode, _BORDERS, "border_", "border mode")
     radius_ = parse_radius(radius)
+    center_ = parse_center(center, swap=swap)
     chain: Any = parse_transformer(transformer)
     # (the reference hashes the option AFTER --swap negated it, cli.py:174-176, 347: str(-0.0) == "-0.0" even for the default)
     tag = unique_suffix(transformer, size, interpolation, border_mode, border_value, radius, merge,
@@ -262,10 +285,15 @@ def lr(
                                                                 **({"progressive": True} if device_decode_progressive else {}))
     if automatch != "":
         match_image = out.with_suffix(f".match{out.suffix}") if savematch else None  # cli.py:362-365
-        chain = calibrated_pair(chain, automatch, left_in, right_in, radius_, match_image)
+        if center_ is not None and isinstance(left_in, Path) and left_in == right_in:
+            # one file holding both eyes: the centres are in each half's own coordinates, so the calibration sees the halves too
+            both = _io.imread(left_in)
+            left_in, right_in = both[:, : both.shape[1] // 2], both[:, both.shape[1] // 2:]
+        chain = calibrated_pair(chain, automatch, left_in, right_in, radius_, match_image, **({} if center_ is None else {"center": center_}))
         LOG.info(f"Automatched transformer: {chain}")
     apply_lr(chain, left_path=left_in, right_path=right_in, out_path=out, radius=radius_, size_output=parse_size(size),
              interpolation=interp, boarder_mode=border, boarder_value=border_value, merge=merge,
+             **({} if center_ is None else {"center": center_}),
              **({"device_png": True} if device_png else {}),
              **({"device_jpeg": "vr180"} if device_vr180 else {"device_jpeg": "batch"} if device_jpeg_batch else {"device_jpeg": True} if device_jpeg else {}),
              **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}),
@@ -282,7 +310,9 @@ def s(
     interpolation: Annotated[str, typer.Option(help="Interpolation method (cv2 name)")] = "inter_lanczos4",
     boarder_mode: Annotated[str, typer.Option(help="Border mode (cv2 name)")] = "border_constant",
     boarder_value: int = 0,
-    radius: Annotated[str, typer.Option(help="Radius of the fisheye image: a number, 'auto' or 'max'")] = "auto",
+    radius: Annotated[str, typer.Option(help="Radius of the fisheye image: a number, 'auto', 'max' or 'fit' (the fitted image circle's)")] = "auto",
+    center: Annotated[str, typer.Option(help="Centre of the image circle in source pixels: 'auto' (fitted per image) or 'X,Y'; "
+                                             "default: the frame's centre")] = "",
     device_png: Annotated[bool, typer.Option("--device-png", help="Deflate .png results on the GPU (larger files, no host codec "
                                                                    "time); other formats and --merge are written by the host")] = False,
     device_jpeg: Annotated[bool, typer.Option("--device-jpeg", help="Encode .jpg / .jpeg results on the GPU (baseline JPEG, quality 95, "
@@ -314,6 +344,7 @@ def s(
     apply(parse_transformer(transformer), in_paths=list(in_paths), out_paths=out_paths, radius=parse_radius(radius),
           size_output=parse_size(size), interpolation=_flag(interpolation, _INTERPOLATIONS, "inter_", "interpolation"),
           boarder_mode=_flag(boarder_mode, _BORDERS, "border_", "border mode"), boarder_value=boarder_value,
+          **({} if center == "" else {"center": parse_center(center, pair=False)}),
           **({"device_png": True} if device_png else {}), **({"device_jpeg": "batch"} if device_jpeg_batch else {"device_jpeg": True} if device_jpeg else {}),
           **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}),
           **({"device_jpeg_optimize": True} if device_jpeg_optimize else {}),

@@ -26,7 +26,7 @@ import torch
 from numpy.typing import NDArray
 
 from . import _abi, _hostpipe, _io, _native
-from .chain import NotLowerable, TransformerBase, get_radius, lower_for_get_map
+from .chain import NotLowerable, TransformerBase, denormalize_center, get_radius, lower_for_get_map
 from .chain import DenormalizeTransformer, NormalizeTransformer
 
 LOG = getLogger(__name__)
@@ -331,14 +331,15 @@ def _split_single_rotation(chain: _abi.Chain) -> tuple[_abi.Chain, np.ndarray | 
     return blank, rot
 
 
-def _host_map(transformer: TransformerBase, *, radius, size_input, size_output):
+def _host_map(transformer: TransformerBase, *, radius, size_input, size_output, center=None):
     """The reference's own recipe (remapper.py:50-58) for chains that cannot be lowered: user
-    subclasses only expose NumPy ``transform``, so the map has to be computed by calling it."""
+    subclasses only expose NumPy ``transform``, so the map has to be computed by calling it.
+    ``center`` = (cx, cy): the image circle's centre instead of ``(W_in // 2, H_in // 2)``."""
     xmap, ymap = np.meshgrid(np.arange(size_output[0]), np.arange(size_output[1]))
     full = (
         NormalizeTransformer()
         * transformer
-        * DenormalizeTransformer(scale=(radius, radius), center=(size_input[1] // 2, size_input[0] // 2))
+        * DenormalizeTransformer(scale=(radius, radius), center=denormalize_center(size_input, center))
     )
     xmap, ymap = full.transform(xmap, ymap)
     return xmap.astype(np.float32), ymap.astype(np.float32)
@@ -408,18 +409,21 @@ def _transformer_key(t: Any):
         return None
 
 
-def _lower_cached(t: TransformerBase, *, radius, size_input, size_output) -> _abi.Chain:
+def _lower_cached(t: TransformerBase, *, radius, size_input, size_output, center=None) -> _abi.Chain:
     """``lower_for_get_map`` memoised on the chain's exact parameter set (``_param_key``): a steady
     stream of identical calls -- frames of a video, bench steps -- lowers once.  Chains holding
-    anything the key cannot capture exactly (user subclasses, object arrays) are lowered every time."""
+    anything the key cannot capture exactly (user subclasses, object arrays) are lowered every time.
+    An explicit ``center`` joins the key by its bits; ``None`` leaves the key what it has always been."""
     k = _transformer_key(t)
     if k is None:
-        return lower_for_get_map(t, radius=radius, size_input=size_input, size_output=size_output)
+        return lower_for_get_map(t, radius=radius, size_input=size_input, size_output=size_output, center=center)
     key = (k, float(radius).hex(), tuple(size_input), tuple(size_output))
+    if center is not None:
+        key += (("center", float(center[0]).hex(), float(center[1]).hex()),)
     with _PLANS_LOCK:  # (the per-device worker threads of sharding.remap_sharded share this cache)
         ch = _LOWERED.get(key)
     if ch is None:
-        ch = lower_for_get_map(t, radius=radius, size_input=size_input, size_output=size_output)
+        ch = lower_for_get_map(t, radius=radius, size_input=size_input, size_output=size_output, center=center)
         with _PLANS_LOCK:
             _LOWERED[key] = ch
             while len(_LOWERED) > 64:
@@ -438,20 +442,27 @@ def remap_tensors(
     boarder_value: Any = 0,
     size_input: tuple[int, int] | None = None,
     rotations: Sequence[Any] | None = None,
+    center: Any = None,
 ) -> list[str]:
     """Device-resident core of ``apply``: remap every ``srcs[k]`` into ``dsts[k]`` (same device,
     same shapes) on the current stream.  ``transformer`` is one chain shared by all units
     (remapper.py:381-398) or one per unit.  ``rotations`` (optional, one 3x3 matrix or quaternion
     per unit) replaces the rotation of the chain's single ``Euclidean3DRotator`` per unit -- the
     per-frame, per-eye calibration of the CLI (cli.py:308-319) without lowering a chain per unit.
+    ``center``: the image circle's centre in source pixels instead of ``(W_in // 2, H_in // 2)`` -- one ``(cx, cy)`` for every unit,
+    one per unit (``None`` entries keep the frame's), or ``"auto"``: fitted from every source (``circle.fit_circle``, rounded to
+    1/4 px; units whose centres agree still share a launch).
     Returns the code path used per launch group ('ray' / 'literal' / 'lut').  Nothing is
-    synchronised."""
+    synchronised (``center="auto"`` synchronises once per source)."""
     n = len(srcs)
     if n == 0:
         return []
+    centers = None
+    if center is not None:
+        centers = per_unit_centers(fit_centers(center, srcs) if isinstance(center, str) else center, n)
     if rotations is not None:
         return _remap_with_rotations(transformer, srcs, dsts, rotations, radius=radius, interpolation=interpolation,
-                                     boarder_mode=boarder_mode, boarder_value=boarder_value, size_input=size_input)
+                                     boarder_mode=boarder_mode, boarder_value=boarder_value, size_input=size_input, centers=centers)
     # one shared transformer, same geometry and parameters as the previous call: straight to its plan
     # (the key is the chain's exact parameter set, see _param_key, and the shape and pixel type of EVERY unit: a call whose units
     #  differ in either -- the halves of an odd-width frame, images of several types -- needs one plan per kind and never matches
@@ -464,6 +475,8 @@ def remap_tensors(
                 units_key = tuple([(s.shape, s.dtype) for s in srcs] + [(d.shape, d.dtype) for d in dsts])
                 memo_key = (tk, float(radius).hex(), units_key, int(interpolation), int(boarder_mode),
                             _border_key(boarder_value, srcs[0].dtype), None if size_input is None else tuple(size_input), srcs[0].device)
+                if centers is not None:
+                    memo_key += (tuple(centers),)
             except (TypeError, ValueError):
                 memo_key = None
             last = _LAST_SHARED[0]  # (one read: another thread may replace the entry at any time)
@@ -478,11 +491,11 @@ def remap_tensors(
             raise TypeError(f"unit {k}: src {s_.dtype} / dst {d_.dtype}: source and destination must have one pixel type")
     cn = int(srcs[0].shape[2])
     dst_wh = (int(dsts[0].shape[1]), int(dsts[0].shape[0]))
-    groups, host_mapped = group_units(transformer, srcs, dsts, radius=radius, size_input=size_input)
+    groups, host_mapped = group_units(transformer, srcs, dsts, radius=radius, size_input=size_input, center=centers)
     paths: list[str] = []
     _TLS.plans = []
     for k, t, size_in_k in host_mapped:
-        xm, ym = _host_map(t, radius=radius, size_input=size_in_k, size_output=dst_wh)
+        xm, ym = _host_map(t, radius=radius, size_input=size_in_k, size_output=dst_wh, center=None if centers is None else centers[k])
         xm_d, ym_d = torch.from_numpy(xm).to(dev), torch.from_numpy(ym).to(dev)
         _check_image_tensor(srcs[k], "src")
         _check_image_tensor(dsts[k], "dst")
@@ -529,10 +542,12 @@ class LaunchGroup:
         self.chain, self.src_hw, self.srcs, self.dsts, self.rots, self.index = chain, src_hw, srcs, dsts, rots, index
 
 
-def group_units(transformer, srcs, dsts, *, radius: float, size_input: tuple[int, int] | None = None):
+def group_units(transformer, srcs, dsts, *, radius: float, size_input: tuple[int, int] | None = None, center: Any = None):
     """Host logic of a call, no device involved: lower the chain of every unit (one shared transformer or
     one per unit), split units into groups that share a plan -- same chain up to the matrix of a single
     rotate stage, same source size, same pixel type -- and list the units whose chain cannot be lowered.
+
+    ``center``: one ``(cx, cy)`` or one per unit (``per_unit_centers``); units with different centres have different chains, hence plans.
 
     Returns ``(groups, host_mapped)``: ``LaunchGroup`` records in first-appearance order and
     ``(unit index, transformer, size_input)`` for units that take the map from their own ``transform()``.
@@ -541,6 +556,7 @@ def group_units(transformer, srcs, dsts, *, radius: float, size_input: tuple[int
     per_unit = list(transformer) if isinstance(transformer, (list, tuple)) else [transformer] * n
     if len(per_unit) != n or len(dsts) != n:
         raise ValueError("need one transformer and one dst per src")
+    centers = per_unit_centers(center, n)
     src_hw = (int(srcs[0].shape[0]), int(srcs[0].shape[1]))
     dst_wh = (int(dsts[0].shape[1]), int(dsts[0].shape[0]))
     acc: "OrderedDict[bytes, dict]" = OrderedDict()
@@ -553,10 +569,11 @@ def group_units(transformer, srcs, dsts, *, radius: float, size_input: tuple[int
         # and W - W // 2 columns
         size_in_k = tuple(size_input) if size_input is not None else (
             src_hw if not isinstance(transformer, (list, tuple)) else (int(srcs[k].shape[0]), int(srcs[k].shape[1])))
-        lk = (id(t), size_in_k)
+        c_k = None if centers is None else centers[k]
+        lk = (id(t), size_in_k, c_k)
         if lk not in lowered:
             try:
-                lowered[lk] = _lower_cached(t, radius=radius, size_input=size_in_k, size_output=dst_wh)
+                lowered[lk] = _lower_cached(t, radius=radius, size_input=size_in_k, size_output=dst_wh, center=c_k)
             except NotLowerable as e:
                 LOG.warning("transformer chain is not lowerable (%s): map evaluated by its own NumPy transform()", e)
                 lowered[lk] = None
@@ -585,7 +602,7 @@ def group_units(transformer, srcs, dsts, *, radius: float, size_input: tuple[int
     return groups, host_mapped
 
 
-def _remap_with_rotations(transformer, srcs, dsts, rotations, *, radius, interpolation, boarder_mode, boarder_value, size_input):
+def _remap_with_rotations(transformer, srcs, dsts, rotations, *, radius, interpolation, boarder_mode, boarder_value, size_input, centers=None):
     from .quat import as_rotation_matrix
 
     if isinstance(transformer, (list, tuple)) or len(rotations) != len(srcs) or len(dsts) != len(srcs):
@@ -593,7 +610,10 @@ def _remap_with_rotations(transformer, srcs, dsts, rotations, *, radius, interpo
     dev = srcs[0].device
     src_hw = (int(srcs[0].shape[0]), int(srcs[0].shape[1]))
     dst_wh = (int(dsts[0].shape[1]), int(dsts[0].shape[0]))
-    chain = lower_for_get_map(transformer, radius=radius, size_input=size_input or src_hw, size_output=dst_wh)
+    if centers is not None and any(c != centers[0] for c in centers):
+        raise ValueError("rotations= shares one plan: it takes ONE center for all units")
+    chain = lower_for_get_map(transformer, radius=radius, size_input=size_input or src_hw, size_output=dst_wh,
+                              center=None if centers is None else centers[0])
     shared, rot = _split_single_rotation(chain)
     if rot is None:
         raise ValueError("rotations= needs a chain with exactly one Euclidean3DRotator")
@@ -614,23 +634,80 @@ def get_map(
     size_input: tuple[int, int],
     size_output: tuple[int, int] = (2048, 2048),
     device: Any = None,
+    center: Any = None,
 ) -> tuple[NDArray[np.float32], NDArray[np.float32]]:
     """Generate the remap map (reference remapper.py:23-59): float32 ``xmap, ymap`` of shape
     ``(size_output[1], size_output[0])``.  Evaluated on the GPU by the same code the fused kernel
-    uses; non-lowerable chains are evaluated through their own ``transform`` like the reference."""
+    uses; non-lowerable chains are evaluated through their own ``transform`` like the reference.
+    ``center`` = (cx, cy): the image circle's centre instead of ``(W_in // 2, H_in // 2)`` (``"auto"`` needs an image: ValueError)."""
     try:
-        chain = lower_for_get_map(transformer, radius=radius, size_input=size_input, size_output=size_output)
+        chain = lower_for_get_map(transformer, radius=radius, size_input=size_input, size_output=size_output, center=center)
     except NotLowerable:
-        return _host_map(transformer, radius=radius, size_input=size_input, size_output=size_output)
+        return _host_map(transformer, radius=radius, size_input=size_input, size_output=size_output, center=center)
     plan = _plan_for(chain, src_hw=(max(1, size_input[0]), max(1, size_input[1])), dst_wh=size_output, cn=3,
                      interpolation=_abi.INTER_LINEAR, border_mode=BORDER_CONSTANT, border_value=0, device=device)
     xm, ym = plan.get_map()
     return xm.cpu().numpy(), ym.cpu().numpy()
 
 
-def get_radius_smart(radius: float | Literal["auto", "max"], images: Sequence[Any]) -> float:
-    """Reference remapper.py:62-90.  ``images`` may be numpy arrays or device tensors."""
-    if isinstance(radius, str) and radius == "auto":
+def _capturing() -> bool:
+    return bool(torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
+
+
+def _is_center_pair(c: Any) -> bool:
+    return (isinstance(c, (tuple, list, np.ndarray)) and len(c) == 2
+            and all(isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) for v in c))
+
+
+def per_unit_centers(center: Any, n: int) -> list | None:
+    """``center=`` of a call with ``n`` units as one entry per unit: ``None`` (every unit keeps ``(W_in // 2, H_in // 2)``), else a list
+    of ``(cx, cy)`` float pairs and ``None`` entries.  Takes ``None``, one pair, or a sequence of ``n`` pairs / ``None``."""
+    if center is None:
+        return None
+    if isinstance(center, str):
+        raise ValueError(f"center={center!r}: resolve it from the images first (fit_centers)")
+    if _is_center_pair(center):
+        return [(float(center[0]), float(center[1]))] * n
+    cs = list(center)
+    if len(cs) != n or not all(c is None or _is_center_pair(c) for c in cs):
+        raise ValueError(f"center must be (cx, cy) or one (cx, cy) / None per image ({n})")
+    out = [None if c is None else (float(c[0]), float(c[1])) for c in cs]
+    return None if all(c is None for c in out) else out
+
+
+def fit_circles(images: Sequence[Any], device: Any = None) -> list:
+    """``circle.fit_circle`` of every image (one synchronisation each); ValueError where an image has no circle"""
+    from . import circle
+
+    return [circle.fit_circle(im, device=device) for im in images]
+
+
+def fit_centers(center: str, images: Sequence[Any], device: Any = None, fits: Sequence[Any] | None = None) -> list[tuple[float, float]]:
+    """``center="auto"``: the fitted centre of every image, each its own, rounded to 1/4 px (the fit is not better than that on real
+    rims, and the frames of one rig then share their plans).  NotImplementedError while the stream is being captured: the plan's tile
+    boxes depend on the centre, which has to visit the host."""
+    from . import circle
+
+    if center != "auto":
+        raise ValueError(f'center must be None, (cx, cy), one per image or "auto", not {center!r}')
+    if _capturing():
+        raise NotImplementedError('center="auto" cannot be captured into a graph (the fitted centre visits the host); pass explicit centres')
+    fits = fit_circles(images, device) if fits is None else fits
+    return [circle.round_center(f.cx, f.cy) for f in fits]
+
+
+def get_radius_smart(radius: float | Literal["auto", "max", "fit"], images: Sequence[Any], *, fits: Sequence[Any] | None = None,
+                     device: Any = None) -> float:
+    """Reference remapper.py:62-90.  ``images`` may be numpy arrays or device tensors.
+    ``"fit"`` (not in the reference): the radius of the fitted image circle (``circle.fit_circle``; ``fits``: the fits where the caller
+    has them already), the maximum over the images, rounded to 1/2 px -- ``get_radius``'s own grid.  It is POSITIVE: it deliberately
+    does not reproduce the sign quirk of ``"auto"``, whose estimate is negative on an image circle on black (the 180-degree flip of the
+    map)."""
+    if isinstance(radius, str) and radius == "fit":
+        from . import circle
+
+        radius_ = max(circle.round_radius(f.radius) for f in (fit_circles(images, device) if fits is None else fits))
+    elif isinstance(radius, str) and radius == "auto":
         radius_ = max(_get_radius_any(im) for im in images)
     elif isinstance(radius, str) and radius == "max":
         radius_ = min(images[0].shape[0] / 2, images[0].shape[1] / 2)
@@ -712,6 +789,7 @@ def apply(
     device_decode: bool | Literal["batch"] = False,
     device_jpeg_optimize: bool = False,
     device_decode_progressive: bool = False,
+    center: Any = None,
 ) -> Sequence[NDArray[np.uint8]]:
     """Apply transformer to images (reference remapper.py:324-403).
 
@@ -732,7 +810,11 @@ def apply(
     each image on the device (``optimize=True`` of jpeg_device.py: smaller files, the same pixels) with either ``device_jpeg`` mode;
     it does nothing without one.  ``device_decode_progressive=True``: with either ``device_decode`` mode, progressive JPEG inputs are
     decoded on the device too (``progressive=True`` of jpeg_decode_device.py; under ``"batch"`` each by a call of its own behind the
-    batch) instead of going to the host reader; it does nothing without ``device_decode``."""
+    batch) instead of going to the host reader; it does nothing without ``device_decode``.
+
+    ``center``: the image circle's centre in source pixels instead of ``(W_in // 2, H_in // 2)`` -- ``(cx, cy)`` for all images, one
+    per image, or ``"auto"``: every image's own, fitted on the device (circle.py) and rounded to 1/4 px.  ``radius="fit"``: the fitted
+    radius (``get_radius_smart``); the radius stays shared, the maximum over the images, whatever the centres."""
     device_jpeg = _device_jpeg_mode(device_jpeg)
     jpeg_kw = {"optimize": True} if device_jpeg_optimize else {}
     in_paths_ = [in_paths] if isinstance(in_paths, (str, Path, np.ndarray, torch.Tensor)) else in_paths
@@ -746,7 +828,17 @@ def apply(
         decoded = next((im for im in images if isinstance(im, torch.Tensor) and im.is_cuda), None)
         if decoded is not None:
             images = [_to_device(im, decoded.device) for im in images]
-    radius_ = get_radius_smart(radius, images)
+    fits = None
+    if (isinstance(radius, str) and radius == "fit") or isinstance(center, str):
+        if isinstance(center, str) and _capturing():
+            fit_centers(center, images)  # (raises)
+        fits = fit_circles(images, device)
+    radius_ = get_radius_smart(radius, images) if fits is None else get_radius_smart(radius, images, fits=fits)
+    centers = per_unit_centers(fit_centers(center, images, fits=fits) if isinstance(center, str) else center, len(images))
+    if centers is not None and all(c == centers[0] for c in centers):
+        center_ = centers[0]  # one centre for all: every route below takes it as it takes the radius
+    else:
+        center_ = centers
     on_device = all(isinstance(im, torch.Tensor) and im.is_cuda for im in images)
     dev = images[0].device if on_device else _device(device)
 
@@ -754,13 +846,13 @@ def apply(
     host_imgs = None if on_device else [np.asarray(im) if not isinstance(im, torch.Tensor) else None for im in images]
     if (host_imgs is not None and _hostpipe.enabled(len(images), len(images) * size_output[0] * size_output[1] * 4) and all(a is not None and a.dtype == np.uint8 and a.ndim in (2, 3)
                                                                         and a.shape == host_imgs[0].shape for a in host_imgs)
-            and boarder_mode != _abi.BORDER_TRANSPARENT):
+            and boarder_mode != _abi.BORDER_TRANSPARENT and (center_ is None or _is_center_pair(center_))):
         imgs3 = [a[..., None] if a.ndim == 2 else a for a in host_imgs]
         size_in = (int(imgs3[0].shape[0]), int(imgs3[0].shape[1]))
 
         def _group(srcs_g, dsts_g):
             remap_tensors(transformer, srcs_g, dsts_g, radius=radius_, interpolation=interpolation, boarder_mode=boarder_mode,
-                          boarder_value=boarder_value, size_input=size_in)
+                          boarder_value=boarder_value, size_input=size_in, center=center_)
 
         results = _hostpipe.run(imgs3, dev, (size_output[1], size_output[0], int(imgs3[0].shape[2])), _group)
         results = [r[..., 0] if a.ndim == 2 else r for r, a in zip(results, host_imgs)]
@@ -775,7 +867,7 @@ def apply(
         for d in dsts:  # cv2 leaves skipped pixels uninitialised; make them deterministic
             d.zero_()
     remap_tensors(transformer, srcs, dsts, radius=radius_, interpolation=interpolation, boarder_mode=boarder_mode,
-                  boarder_value=boarder_value, size_input=(int(srcs[0].shape[0]), int(srcs[0].shape[1])))
+                  boarder_value=boarder_value, size_input=(int(srcs[0].shape[0]), int(srcs[0].shape[1])), center=center_)
     if on_device:
         results: list[Any] = dsts
     else:
@@ -826,7 +918,7 @@ def auto_radius_tensor(images: Sequence[torch.Tensor], threshold: int = 10) -> t
 
 def remap_tensors_auto(transformer: TransformerBase, srcs: Sequence[torch.Tensor], dsts: Sequence[torch.Tensor], *,
                        rad: torch.Tensor | None = None, interpolation: int = INTER_LANCZOS4, boarder_mode: int = BORDER_CONSTANT,
-                       boarder_value: Any = 0, size_input: tuple[int, int] | None = None) -> None:
+                       boarder_value: Any = 0, size_input: tuple[int, int] | None = None, center: Any = None) -> None:
     """``remap_tensors`` with ``radius="auto"`` -- the reference's default, remapper.py:333 -- and the radius never leaving the device:
     estimated from ``srcs`` (or given as ``rad``, ``auto_radius_tensor``), the maximum taken and the Denormalize scale set by ONE small
     launch in front of the remap launch (``v1c_plan_run_auto_images`` / ``v1c_plan_run_auto``).  No stream synchronisation, no
@@ -838,7 +930,11 @@ def remap_tensors_auto(transformer: TransformerBase, srcs: Sequence[torch.Tensor
     ``remap_tensors``: one radius over all of them (``auto_radius_tensor``), one launch per source shape (``auto_groups``).
     Raises NotImplementedError for chains the device-resident form does not serve (see include/vr180_remap.h), chains that cannot be
     lowered among them; a decline after the first of several shape groups has run leaves that group's outputs written (with the very
-    bytes the caller's fallback writes again)."""
+    bytes the caller's fallback writes again).
+    ``center`` = (cx, cy): ONE explicit image-circle centre for every source instead of ``(W_in // 2, H_in // 2)`` (a fitted one would
+    have to visit the host: ``center="auto"`` is refused)."""
+    if center is not None and not _is_center_pair(center):
+        raise NotImplementedError("remap_tensors_auto takes ONE explicit center (cx, cy): the plan's boxes depend on it")
     if isinstance(transformer, (list, tuple)):
         raise ValueError("remap_tensors_auto takes ONE transformer (per-eye transformers: one call per eye, as apply_lr does)")
     if any(s.dtype != torch.uint8 for s in srcs):
@@ -850,7 +946,8 @@ def remap_tensors_auto(transformer: TransformerBase, srcs: Sequence[torch.Tensor
     size_in = tuple(size_input) if size_input is not None else src_hw
     nominal = min(size_in[0] / 2, size_in[1] / 2)  # (any radius: the launch ignores the plan's own)
     try:
-        chain = _lower_cached(transformer, radius=nominal, size_input=size_in, size_output=dst_wh)
+        chain = _lower_cached(transformer, radius=nominal, size_input=size_in, size_output=dst_wh,
+                              center=None if center is None else (float(center[0]), float(center[1])))
     except NotLowerable as e:  # (the callers' fallback, remap_tensors, serves it from the chain's own transform(): the LUT path)
         raise NotImplementedError(f"remap_tensors_auto: the chain cannot be lowered ({e})") from e
     groups = auto_groups(srcs)
@@ -917,6 +1014,7 @@ def apply_lr_tensors(
     boarder_value: Any = 0,
     radius: float | Literal["auto", "max"] = "auto",
     auto_radius_on_device: bool | None = None,
+    center: Any = None,
 ) -> torch.Tensor:
     """Device-resident ``apply_lr`` (merge=False): both eyes are remapped by ONE launch straight
     into the halves of the ``(H, 2W, C)`` side-by-side tensor (remapper.py:460-484, 517-518).
@@ -929,9 +1027,26 @@ def apply_lr_tensors(
 
     uint16 / float32 eyes give an output of their type.  Their radius="auto" always takes the exact form (the device-resident one is
     8-bit only): under graph capture with ``auto_radius_on_device=None`` the NotImplementedError of ``remap_tensors_auto`` propagates,
-    as it does for chains that form does not serve -- pass a numeric radius there."""
+    as it does for chains that form does not serve -- pass a numeric radius there.
+
+    ``center``: the image circles' centres in source pixels instead of ``(W_in // 2, H_in // 2)`` -- one ``(cx, cy)`` for both eyes,
+    ``((lx, ly), (rx, ry))`` per eye (each in its own eye's coordinates), or ``"auto"``: each eye's own, fitted on the device and rounded
+    to 1/4 px (circle.py).  Eyes whose centres differ are remapped by a launch each.  ``"auto"`` needs the fitted centres on the host
+    (the plan's tile boxes depend on them): NotImplementedError under stream capture and with ``auto_radius_on_device=True``; explicit
+    centres work in both.  ``radius="fit"``: the fitted radius (``get_radius_smart``), positive; ``radius="auto"`` keeps its value,
+    sign included, whatever ``center``."""
     w, h = size_output
     cn = left.shape[2]
+    fits = None
+    if isinstance(center, str):
+        if auto_radius_on_device:
+            raise NotImplementedError('center="auto" takes the fitted centres to the host: it does not go with auto_radius_on_device=True')
+        fits = None if _capturing() else fit_circles([left, right])
+        center = fit_centers(center, [left, right], fits=fits)
+    elif isinstance(radius, str) and radius == "fit":
+        fits = fit_circles([left, right])
+    centers = per_unit_centers(center, 2)
+    same_center = centers is None or centers[0] == centers[1]
     if out is None:
         out = torch.empty((h, 2 * w, cn), dtype=left.dtype, device=left.device)
         if boarder_mode == _abi.BORDER_TRANSPARENT:
@@ -944,11 +1059,20 @@ def apply_lr_tensors(
         if on_dev:
             try:
                 if isinstance(transformer, tuple):  # per-eye transformer AND per-eye radius (remapper.py:460-473)
-                    for t, im, d in zip(transformer, (left, right), halves):
-                        remap_tensors_auto(t, [im], [d], interpolation=interpolation, boarder_mode=boarder_mode, boarder_value=boarder_value)
-                else:
+                    for k, (t, im, d) in enumerate(zip(transformer, (left, right), halves)):
+                        remap_tensors_auto(t, [im], [d], interpolation=interpolation, boarder_mode=boarder_mode, boarder_value=boarder_value,
+                                           center=None if centers is None else centers[k])
+                elif same_center:
                     remap_tensors_auto(transformer, [left, right], halves, interpolation=interpolation, boarder_mode=boarder_mode,
-                                       boarder_value=boarder_value, size_input=(int(left.shape[0]), int(left.shape[1])))
+                                       boarder_value=boarder_value, size_input=(int(left.shape[0]), int(left.shape[1])),
+                                       center=None if centers is None else centers[0])
+                else:  # a centre per eye: a launch per eye, ONE radius over both (the maximum, as get_radius_smart has it)
+                    if left.dtype != torch.uint8 or right.dtype != torch.uint8:
+                        raise NotImplementedError("remap_tensors_auto: 8-bit images only (16-bit / float32: the radius goes to the host)")
+                    rad = auto_radius_tensor([left, right])
+                    for k, (im, d) in enumerate(zip((left, right), halves)):
+                        remap_tensors_auto(transformer, [im], [d], rad=rad, interpolation=interpolation, boarder_mode=boarder_mode,
+                                           boarder_value=boarder_value, size_input=(int(left.shape[0]), int(left.shape[1])), center=centers[k])
                 _TLS.auto_form = "device"
                 return out
             except NotImplementedError:
@@ -958,18 +1082,22 @@ def apply_lr_tensors(
         _TLS.auto_form = "exact"
     if isinstance(transformer, tuple):
         # per-eye transformer AND per-eye radius estimate (remapper.py:460-473)
-        r = [get_radius_smart(radius, [im]) for im in (left, right)]
+        r = [get_radius_smart(radius, [im]) if fits is None else get_radius_smart(radius, [im], fits=[f])
+             for im, f in zip((left, right), fits or (None, None))]
         if r[0] == r[1]:
             remap_tensors(list(transformer), [left, right], halves, radius=r[0], interpolation=interpolation,
-                          boarder_mode=boarder_mode, boarder_value=boarder_value)
+                          boarder_mode=boarder_mode, boarder_value=boarder_value, center=centers)
         else:
-            for t, im, d, rr in zip(transformer, (left, right), halves, r):
+            for k, (t, im, d, rr) in enumerate(zip(transformer, (left, right), halves, r)):
                 remap_tensors(t, [im], [d], radius=rr, interpolation=interpolation, boarder_mode=boarder_mode,
-                              boarder_value=boarder_value)
+                              boarder_value=boarder_value, center=None if centers is None else centers[k])
     else:
-        r_ = get_radius_smart(radius, [left, right])
+        r_ = get_radius_smart(radius, [left, right]) if fits is None else get_radius_smart(radius, [left, right], fits=fits)
         size_in = (int(left.shape[0]), int(left.shape[1]))
-        if not (isinstance(radius, str) and radius == "auto" and
+        if centers is not None:  # (the launch that reads a moved radius from device memory is keyed without a centre: the planned path)
+            remap_tensors(transformer, [left, right], halves, radius=r_, interpolation=interpolation,
+                          boarder_mode=boarder_mode, boarder_value=boarder_value, size_input=size_in, center=centers)
+        elif not (isinstance(radius, str) and radius == "auto" and
                 _remap_host_radius(transformer, [left, right], halves, float(r_), interpolation=interpolation, boarder_mode=boarder_mode,
                                    boarder_value=boarder_value, size_input=size_in)):
             remap_tensors(transformer, [left, right], halves, radius=r_, interpolation=interpolation,
@@ -1013,6 +1141,7 @@ def apply_lr(
     device_decode: bool | Literal["batch"] = False,
     device_jpeg_optimize: bool = False,
     device_decode_progressive: bool = False,
+    center: Any = None,
 ) -> None:
     """Apply transformer to a pair of images and save them side by side (reference
     remapper.py:406-520).  ``left_path == right_path`` means one file holding both eyes.
@@ -1030,7 +1159,10 @@ def apply_lr(
     uploaded; one file holding both eyes is decoded once and the halves are views of it.  Files outside the device decoder's scope
     are read by the host as before.  ``device_decode="batch"``: the same, with the two files decoded as one batch of two.
     ``device_decode_progressive=True``: with either mode, progressive JPEG inputs are decoded on the device too instead of going to the
-    host reader (``progressive=True`` of jpeg_decode_device.py)."""
+    host reader (``progressive=True`` of jpeg_decode_device.py).
+    ``center``: as in ``apply_lr_tensors`` -- ``(cx, cy)``, a pair of them per eye, or ``"auto"``.  With one file holding both eyes the
+    centres are in each HALF's own coordinates, and ``"auto"`` fits each half: the circles of a side-by-side fisheye frame are nowhere
+    near ``W // 2`` of their halves."""
     vr180 = isinstance(device_jpeg, str) and device_jpeg == "vr180"
     device_jpeg = True if vr180 else _device_jpeg_mode(device_jpeg)
     if vr180 and merge:
@@ -1056,7 +1188,7 @@ def apply_lr(
     # "auto" radius: estimated on the host images when they are numpy (one row each)
     sbs = apply_lr_tensors(transformer, lt, rt, size_output=size_output, interpolation=interpolation,
                            boarder_mode=boarder_mode, boarder_value=boarder_value,
-                           radius=_radius_for_pair(radius, transformer, left, right))
+                           radius=_radius_for_pair(radius, transformer, left, right), center=center)
     if merge and sbs.dtype != torch.uint8:
         # 16-bit / float32: the reference's own NumPy expression (remapper.py:485-497) on the host copy (the anaglyph kernel is 8-bit)
         w = size_output[0]
