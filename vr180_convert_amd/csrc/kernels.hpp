@@ -119,7 +119,11 @@ int tile_mirror_raw_passes(const void* host_boxes, const void* host_mboxes, cons
 // four-buffer / register-staged A/B partners
 hipError_t launch_ray_lin3_pair_mirror(const KernelCtx& c, const KernelCtx* cdev, const LaunchUnits& lu, uint32_t* flags, const void* boxes,
                                        const void* mboxes, int half_dwords, int mirror_h, const uint32_t* rest_list, int n_rest, int raw_nwp,
-                                       hipStream_t stream, int seq_kb);
+                                       hipStream_t stream, int seq_kb, const void* recs = nullptr);
+// The launch records of the seq and one-eye kernels (tile_device.hpp: MirrorRec), 64 bytes per tile in the order of the boxes: what a
+// tile pair's prologue derives from the plan alone, from the downloaded boxes.  `seq_kb` / `one_kb`: the two kernels' box buffers (0:
+// the plan does not launch that kernel).  `recs` of the launch: the uploaded records.
+void tile_mirror_records(const void* host_boxes, const void* host_mboxes, size_t n_tiles, const Geom& g, int seq_kb, int one_kb, std::vector<char>& out);
 int tile_half_dwords(const void* host_boxes, size_t n_tiles, int max_chunks, bool occupancy_classes);
 // `coords_bounded` (launches without boxes): the host has bounded |32 x|, |32 y| < 2^21 for every pixel of every unit
 // (radial_table_g_bound): k_ray_lin3_rot_pair_raw evaluates its speculative coordinates without the clamps of the cvRound trick

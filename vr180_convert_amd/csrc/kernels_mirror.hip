@@ -1,6 +1,13 @@
 // kernels_mirror.hip -- pairs (apply_lr) and single images of an unrotated chain: one workgroup serves a tile AND the band that
 // mirrors it about the equator from one set of coordinates, the boxes brought in by LDS-DMA (k_ray_lin3_pair_mirror_seq: pairs, the
 // eyes one after the other through two buffers; k_ray_lin3_pair_mirror_raw: single images; their A/B partners in the tuning build).
+// The prologue of the seq and one-eye kernels: the tile from the preloaded head (xcd_tile_at), its row / column loads, then ONE scalar
+// load of the tile pair's launch record (MirrorRec, tile_device.hpp) -- fit verdict, table slice, and per box: rows, units per row,
+// rows per pass, lanes per pass, the magic of lane -> (row, unit) and the biased origin of the tap addresses -- which plan.hip
+// encodes once per plan from the boxes it downloads (tile_mirror_records below).  What is left in the kernel of that arithmetic is
+// what belongs to the call: the products with the source and destination pitches.  The A/B partners of the tuning build
+// (V1C_MIRROR_REC=0: k_ray_lin3_pair_mirror_seq_box, k_ray_lin3_pair_mirror_box_raw) keep the prologue that decodes the (tile box,
+// band box) pair, tests mirror_raw_fit and takes the reciprocals of the units per row in every wave.
 // Building blocks: tile_device.hpp.
 #include "tile_device.hpp"
 
@@ -108,12 +115,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) voi
 
 // NE = number of eyes (units) of the launch: 2 = apply_lr's pair; 1 = a single image (apply() of one image, BASELINE config 1):
 // the same workgroup with two boxes instead of four
-template <int VAR_W, int NE = 2>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V1C_RAW_WAVES, 8))) void k_ray_lin3_pair_mirror_raw(V1C_MIRROR_HEAD, TileArgs a_)
+// REC = 1 (the one-eye form): the prologue from the plan's launch record, as in k_ray_lin3_pair_mirror_seq (mirror_seq_tile below)
+template <int VAR_W, int NE, int REC>
+__device__ __forceinline__ void mirror_raw_tile(V1C_MIRROR_HEAD, double* tabw, uint32_t* dyn_box)
 {
+    static_assert(!REC || NE == 1, "the record serves the one-eye form");
     constexpr int NT = 256;
-    __shared__ __attribute__((aligned(16))) double tabw[kTabSlice * kRadialCoefs];
-    extern __shared__ __attribute__((aligned(16))) uint32_t dyn_box[];  // 2 NE raw boxes (or the general code's cell buffers)
     if (V1C_PRIO & 4)
         __builtin_amdgcn_s_setprio(3);
     args_cref a = kernel_args<kMirrorHeadBytes>();
@@ -134,7 +141,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V1C_RAW_WAV
     // load) are requested before the argument block has been read at all
     int tx, ty;
     {
-        const unsigned slen = (rows_strip >> 16) * tiles_x;  // strips of 0 / 2 tile rows; floor(2^32 / (2 t)) == floor(floor(2^32 / t) / 2)
+        // strips of 0 / 2 tile rows; floor(2^32 / (2 t)) == floor(floor(2^32 / t) / 2)
+        // (REC: the mask tells the compiler what the host knows -- never xcd_tile_at's block mode, whose two divisions then leave the text)
+        const unsigned slen = ((rows_strip >> 16) * tiles_x) & (REC ? 0x7fffffffu : 0xffffffffu);
         xcd_tile_at(tiles_x_magic, slen, ((tiles_x_magic - 1u) >> 1) + 1u, tx, ty, rows_strip & 0xffffu, rest_rows, tiles_x, 0u);
     }
     // tile rows 0 .. TY / 2: row 0 of the image has no mirror image (its band row would be row H: not stored), row H / 2 is its
@@ -143,7 +152,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V1C_RAW_WAV
     const TileIds t = tile_ids(dsz, 0, tid, tx, ty, (int)tiles_x, NT / kLanesX);
     RowCol rc;
     load_rowcol<0>(rowcol_tables_at(rowcol_tables, dsz.dst_w, dsz.dst_h), t.xc, t.jc, rc);
-    const TileBoxPair bq = load_tile_box_pair(pairs, t.box_tile);
+    TileBoxPair bq{};
+    MirrorRec r{};
+    if constexpr (REC)
+        r = load_mirror_rec(pairs, t.box_tile);
+    else
+        bq = load_tile_box_pair(pairs, t.box_tile);
     const TileBox &b = bq.b, &q = bq.q;
     ctx_cref c = *(const V1C_CONST KernelCtx*)ctxp;
     const units_cptr U = (units_cptr)a.inl;  // (one or two units: always the block's own records, at a known offset)
@@ -151,9 +165,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V1C_RAW_WAV
     ray_cref P = c.ray;
     touch_plan_and_units<0, NE>(c, U, 0, NE - 1);
     const int nwp = (int)(kb_mh & 0xffffu);
-    if (mirror_raw_fit(b, q, nwp, g.src_h, g.src_w) != 1)
+    if (REC ? !(r.flags & kMirrorRecFitOne) : mirror_raw_fit(b, q, nwp, g.src_h, g.src_w) != 1)
         return;
-    const bool mpoly = (b.interior & 2) != 0;
+    const bool mpoly = REC ? (r.flags & kMirrorRecMpoly) != 0 : (b.interior & 2) != 0;
+    const int idx0 = REC ? r.idx0 : b.idx0, nidx = REC ? r.nidx : b.nidx;
     // (the row / column values are consumed here: the compiler's own wait for them then sits in front of the DMA requests,
     // not -- as vmcnt(0), it does not count LDS-DMA -- in front of the coordinates)
 #pragma unroll
@@ -166,32 +181,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V1C_RAW_WAV
     const uint32_t raw_b = (uint32_t)(uintptr_t)(lds_u32_ptr)dyn_box, raw_q = raw_b + (uint32_t)NE * box_bytes;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     {  // table slice: nidx * 4 units of 16 bytes, one pass (units past the slice: clamped, they land in the unused tail of tabw)
-        const uint32_t u = min((uint32_t)tid, (uint32_t)(b.nidx * 4 - 1));
-        const uint8_t* gp = (const uint8_t*)(radial_table(P, mpoly) + (size_t)b.idx0 * kRadialCoefs) + u * 16u;
+        const uint32_t u = min((uint32_t)tid, (uint32_t)(nidx * 4 - 1));
+        const uint8_t* gp = (const uint8_t*)(radial_table(P, mpoly) + (size_t)idx0 * kRadialCoefs) + u * 16u;
         __builtin_amdgcn_global_load_lds((glb_void_ptr)gp, (lds_void_ptr)(uintptr_t)(lds_tab + (uint32_t)__builtin_amdgcn_readfirstlane(tid & ~63) * 16u), 16, 0, 0);
     }
-    const RawLanes mb = raw_lanes(b.cpr, lane), mq = raw_lanes(q.cpr, lane);
+    const RawLanes mb = REC ? rec_lanes(r.b, lane) : raw_lanes(b.cpr, lane), mq = REC ? rec_lanes(r.q, lane) : raw_lanes(q.cpr, lane);
     const uint32_t row_off = (uint32_t)t.x0 * 3u;
     const int mirror_h = (int)(kb_mh >> 16);
     const int jm = mirror_h - t.j;              // the band's row
     const bool band_row = jm < dsz.dst_h;         // (false for row 0 of the image only)
     LaneCoords L;
     uint32_t p0[kPX], p1[kPX];
-    const int nb = raw_box_dma(b, mb, U[0].src, (uint32_t)U[0].src_pitch, lane, wave, raw_b);  // this wave's requests per box of the tile ...
-    if (NE == 2)
-        raw_box_dma(b, mb, U[NE - 1].src, (uint32_t)U[NE - 1].src_pitch, lane, wave, raw_b + box_bytes);
-    const int nq = raw_box_dma(q, mq, U[0].src, (uint32_t)U[0].src_pitch, lane, wave, raw_q);  // ... and of the mirrored band
-    if (NE == 2)
-        raw_box_dma(q, mq, U[NE - 1].src, (uint32_t)U[NE - 1].src_pitch, lane, wave, raw_q + box_bytes);
+    int nb, nq;
+    if constexpr (REC) {
+        nb = rec_box_dma(r.b, mb, U[0].src, (uint32_t)U[0].src_pitch, lane, wave, raw_b);
+        nq = rec_box_dma(r.q, mq, U[0].src, (uint32_t)U[0].src_pitch, lane, wave, raw_q);
+    } else {
+        nb = raw_box_dma(b, mb, U[0].src, (uint32_t)U[0].src_pitch, lane, wave, raw_b);  // this wave's requests per box of the tile ...
+        if (NE == 2)
+            raw_box_dma(b, mb, U[NE - 1].src, (uint32_t)U[NE - 1].src_pitch, lane, wave, raw_b + box_bytes);
+        nq = raw_box_dma(q, mq, U[0].src, (uint32_t)U[0].src_pitch, lane, wave, raw_q);  // ... and of the mirrored band
+        if (NE == 2)
+            raw_box_dma(q, mq, U[NE - 1].src, (uint32_t)U[NE - 1].src_pitch, lane, wave, raw_q + box_bytes);
+    }
     if (V1C_PRIO & 4)
         __builtin_amdgcn_s_setprio(0);
     // Barriers without __syncthreads()' fence (it would wait for every load in flight): each wave waits for its own part of
     // what the barrier publishes -- vmcnt counts in issue order -- then joins.
     wait_vm_barrier(NE * (nb + nq));  // table slice landed (this wave's box loads may still be in flight)
     if (mpoly)
-        lane_coords<VAR_W, 0, 2, 0, 1, 1, 1>(c, nullptr, rc, kPX, (const double*)tabw, b.idx0, b.nidx, L);
+        lane_coords<VAR_W, 0, 2, 0, 1, 1, 1, 0, REC>(c, nullptr, rc, kPX, (const double*)tabw, idx0, nidx, L);
     else
-        lane_coords<VAR_W, 0, 2, 0, 1, 0, 1>(c, nullptr, rc, kPX, (const double*)tabw, b.idx0, b.nidx, L);
+        lane_coords<VAR_W, 0, 2, 0, 1, 0, 1, 0, REC>(c, nullptr, rc, kPX, (const double*)tabw, idx0, nidx, L);
     wait_vm_barrier(NE * nq);  // the tile's boxes
     if constexpr (NE == 2) {
         gather_pair_raw(b, raw_b, box_bytes, L.sx, L.sy, p0, p1);
@@ -201,6 +222,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V1C_RAW_WAV
         gather_pair_raw(q, raw_q, box_bytes, L.sx, L.sy2, p0, p1);
         if (band_row)
             store_pair_row(U, t, jm, p0, p1);
+    } else if constexpr (REC) {
+        gather_one_rec(r.b, raw_b, L.sx, L.sy, p0);
+        wait_vm_barrier_imm<0>();
+        store4<1>(U[0].dst + (mul24_vs((uint32_t)t.j, (uint32_t)U[0].dst_pitch) + row_off), p0, 0xFu, dst_rows_dword_aligned(U, 0));
+        gather_one_rec(r.q, raw_q, L.sx, L.sy2, p1);
+        if (band_row)
+            store4<1>(U[0].dst + (mul24_vs((uint32_t)jm, (uint32_t)U[0].dst_pitch) + row_off), p1, 0xFu, dst_rows_dword_aligned(U, 0));
     } else {
         gather_one_raw(b, raw_b, L.sx, L.sy, p0);
         wait_vm_barrier_imm<0>();
@@ -210,6 +238,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V1C_RAW_WAV
             store4<1>(U[0].dst + (__umul24((uint32_t)jm, (uint32_t)U[0].dst_pitch) + row_off), p1, 0xFu, dst_rows_dword_aligned(U, 0));
     }
 }
+
+template <int VAR_W, int NE = 2>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V1C_RAW_WAVES, 8))) void k_ray_lin3_pair_mirror_raw(V1C_MIRROR_HEAD, TileArgs a_)
+{
+    __shared__ __attribute__((aligned(16))) double tabw[kTabSlice * kRadialCoefs];
+    extern __shared__ __attribute__((aligned(16))) uint32_t dyn_box[];  // 2 NE raw boxes (or the general code's cell buffers)
+    mirror_raw_tile<VAR_W, NE, NE == 1>(pairs, tiles_x_magic, gx_rest, rows_strip, dst_wh, rowcol_tables, ctxp, kb_mh, tabw, dyn_box);
+}
+#ifdef V1C_TUNING  // (V1C_MIRROR_REC=0: the one-eye form on the plain box pairs)
+template <int VAR_W>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V1C_RAW_WAVES, 8))) void k_ray_lin3_pair_mirror_box_raw(V1C_MIRROR_HEAD, TileArgs a_)
+{
+    __shared__ __attribute__((aligned(16))) double tabw[kTabSlice * kRadialCoefs];
+    extern __shared__ __attribute__((aligned(16))) uint32_t dyn_box[];
+    mirror_raw_tile<VAR_W, 1, 0>(pairs, tiles_x_magic, gx_rest, rows_strip, dst_wh, rowcol_tables, ctxp, kb_mh, tabw, dyn_box);
+}
+#endif
 
 // ---- the pair kernel with the eyes one after the other: two box buffers instead of four ----
 // k_ray_lin3_pair_mirror_raw holds four boxes (two eyes x tile and band) in LDS at once.  Here the workgroup keeps two buffers (tile
@@ -235,15 +280,16 @@ __device__ __forceinline__ void gather_taps_raw(const uint32_t (&ta)[kPX], const
     }
 }
 
-// REST = 0: the plan's rest list is empty (C2: every tile pair fits) -- the instantiation without the general pair code, whose
-// registers (74 against 68 VGPRs, 94 against 66 SGPRs) and LDS (its cell buffers) otherwise set the occupancy of a launch that never
-// runs it: 7 instead of 6 workgroups per CU
-template <int VAR_W, int REST = 1>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(REST ? V1C_SEQ_WAVES : V1C_SEQ_WAVES + 1, 8))) void k_ray_lin3_pair_mirror_seq(V1C_MIRROR_HEAD, TileArgs a_)
+// REC = 1: the prologue from the plan's launch record (MirrorRec, tile_device.hpp): fit verdict, units per row, rows per pass, the
+// lanes' (row, unit) of a pass by a 16-bit magic and the biased box origins of the tap addresses come out of the record's one scalar
+// load; the coordinates stay the rounding trick's raw bits (lane_coords<..., BIASED>), a tap address is one shift and one 24-bit
+// multiply-add per box on top of the 3 (bx >> 5) both boxes share, and the destination row offsets are 24-bit multiplies too.
+// REC = 0 (tuning build, V1C_MIRROR_REC=0): the prologue that decodes the (tile box, band box) pair in every wave -- the A/B partner.
+// Requests, stores and waits are the same in both: row / column loads, table slice, b, q | ... (see above).
+template <int VAR_W, int REST, int REC>
+__device__ __forceinline__ void mirror_seq_tile(V1C_MIRROR_HEAD, double* tabw, uint32_t* dyn_box)
 {
     constexpr int NT = 256;
-    __shared__ __attribute__((aligned(16))) double tabw[kTabSlice * kRadialCoefs];
-    extern __shared__ __attribute__((aligned(16))) uint32_t dyn_box[];  // 2 raw boxes of a.kb KB (or the general code's cell buffers)
     if (V1C_PRIO & 4)
         __builtin_amdgcn_s_setprio(3);
     args_cref a = kernel_args<kMirrorHeadBytes>();
@@ -260,11 +306,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(REST ? V1C_
             return;
         }
     }
-    // from the preloaded head alone (V1C_MIRROR_HEAD): the tile, its row / column values (vector loads) and its pair of boxes (one scalar
+    // from the preloaded head alone (V1C_MIRROR_HEAD): the tile, its row / column values (vector loads) and its record (one scalar
     // load) are requested before the argument block has been read at all
     int tx, ty;
     {
-        const unsigned slen = (rows_strip >> 16) * tiles_x;  // strips of 0 / 2 tile rows; floor(2^32 / (2 t)) == floor(floor(2^32 / t) / 2)
+        // strips of 0 / 2 tile rows; floor(2^32 / (2 t)) == floor(floor(2^32 / t) / 2)
+        // (REC: the mask tells the compiler what the host knows -- never xcd_tile_at's block mode, whose two divisions then leave the text)
+        const unsigned slen = ((rows_strip >> 16) * tiles_x) & (REC ? 0x7fffffffu : 0xffffffffu);
         xcd_tile_at(tiles_x_magic, slen, ((tiles_x_magic - 1u) >> 1) + 1u, tx, ty, rows_strip & 0xffffu, rest_rows, tiles_x, 0u);
     }
     // tile rows 0 .. TY / 2: row 0 of the image has no mirror image (its band row would be row H: not stored), row H / 2 is its
@@ -273,7 +321,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(REST ? V1C_
     const TileIds t = tile_ids(dsz, 0, tid, tx, ty, (int)tiles_x, NT / kLanesX);
     RowCol rc;
     load_rowcol<0>(rowcol_tables_at(rowcol_tables, dsz.dst_w, dsz.dst_h), t.xc, t.jc, rc);
-    const TileBoxPair bq = load_tile_box_pair(pairs, t.box_tile);
+    TileBoxPair bq{};
+    MirrorRec r{};
+    if constexpr (REC)
+        r = load_mirror_rec(pairs, t.box_tile);
+    else
+        bq = load_tile_box_pair(pairs, t.box_tile);
     const TileBox &b = bq.b, &q = bq.q;
     ctx_cref c = *(const V1C_CONST KernelCtx*)ctxp;
     const units_cptr U = (units_cptr)a.inl;  // (one or two units: always the block's own records, at a known offset)
@@ -281,9 +334,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(REST ? V1C_
     ray_cref P = c.ray;
     touch_plan_and_units<0, 2>(c, U, 0, 1);
     const int cap_kb = (int)(kb_mh & 0xffffu);
-    if (mirror_raw_fit(b, q, cap_kb, g.src_h, g.src_w) != 1)
+    if (REC ? !(r.flags & kMirrorRecFitSeq) : mirror_raw_fit(b, q, cap_kb, g.src_h, g.src_w) != 1)
         return;
-    const bool mpoly = (b.interior & 2) != 0;
+    const bool mpoly = REC ? (r.flags & kMirrorRecMpoly) != 0 : (b.interior & 2) != 0;
+    const int idx0 = REC ? r.idx0 : b.idx0, nidx = REC ? r.nidx : b.nidx;
 #pragma unroll
     for (int k = 0; k < kPX; k++)
         asm volatile("" ::"v"(rc.slon[k]), "v"(rc.qlon[k]));
@@ -292,30 +346,46 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(REST ? V1C_
     const uint32_t raw_b = (uint32_t)(uintptr_t)(lds_u32_ptr)dyn_box, raw_q = raw_b + (uint32_t)cap_kb * 1024u;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     {
-        const uint32_t u = min((uint32_t)tid, (uint32_t)(b.nidx * 4 - 1));
-        const uint8_t* gp = (const uint8_t*)(radial_table(P, mpoly) + (size_t)b.idx0 * kRadialCoefs) + u * 16u;
+        const uint32_t u = min((uint32_t)tid, (uint32_t)(nidx * 4 - 1));
+        const uint8_t* gp = (const uint8_t*)(radial_table(P, mpoly) + (size_t)idx0 * kRadialCoefs) + u * 16u;
         __builtin_amdgcn_global_load_lds((glb_void_ptr)gp, (lds_void_ptr)(uintptr_t)(lds_tab + (uint32_t)__builtin_amdgcn_readfirstlane(tid & ~63) * 16u), 16, 0, 0);
     }
-    const RawLanes mb = raw_lanes(b.cpr, lane), mq = raw_lanes(q.cpr, lane);
-    const int nb = raw_box_dma(b, mb, U[0].src, (uint32_t)U[0].src_pitch, lane, wave, raw_b);
-    const int nq = raw_box_dma(q, mq, U[0].src, (uint32_t)U[0].src_pitch, lane, wave, raw_q);
+    const RawLanes mb = REC ? rec_lanes(r.b, lane) : raw_lanes(b.cpr, lane), mq = REC ? rec_lanes(r.q, lane) : raw_lanes(q.cpr, lane);
+    // one eye's (tile box, band box) requests; returns the band's count (the tile's in `nb`)
+    auto request = [&](int e, int which) {
+        const uint8_t* src = U[e].src;
+        const uint32_t sp = (uint32_t)U[e].src_pitch;
+        if constexpr (REC)
+            return which == 0 ? rec_box_dma(r.b, mb, src, sp, lane, wave, raw_b) : rec_box_dma(r.q, mq, src, sp, lane, wave, raw_q);
+        else
+            return which == 0 ? raw_box_dma(b, mb, src, sp, lane, wave, raw_b) : raw_box_dma(q, mq, src, sp, lane, wave, raw_q);
+    };
+    const int nb = request(0, 0);
+    const int nq = request(0, 1);
     if (V1C_PRIO & 4)
         __builtin_amdgcn_s_setprio(0);
     wait_vm_barrier(nb + nq);  // table slice
-    const uint32_t pitch_b = (uint32_t)raw_units_per_row(b.cpr) * 16u, pitch_q = (uint32_t)raw_units_per_row(q.cpr) * 16u;
+    const uint32_t pitch_b = REC ? r.b.lpitch : (uint32_t)raw_units_per_row(b.cpr) * 16u, pitch_q = REC ? r.q.lpitch : (uint32_t)raw_units_per_row(q.cpr) * 16u;
     uint32_t ta_b[kPX], ta_q[kPX];
     BlendW W_b[kPX], W_q[kPX];
     {
         LaneCoords L;
         if (mpoly)
-            lane_coords<VAR_W, 0, 2, 0, 1, 1, 1>(c, nullptr, rc, kPX, (const double*)tabw, b.idx0, b.nidx, L);
+            lane_coords<VAR_W, 0, 2, 0, 1, 1, 1, 0, REC>(c, nullptr, rc, kPX, (const double*)tabw, idx0, nidx, L);
         else
-            lane_coords<VAR_W, 0, 2, 0, 1, 0, 1>(c, nullptr, rc, kPX, (const double*)tabw, b.idx0, b.nidx, L);
+            lane_coords<VAR_W, 0, 2, 0, 1, 0, 1, 0, REC>(c, nullptr, rc, kPX, (const double*)tabw, idx0, nidx, L);
+        const uint32_t kb = r.b.tapk + raw_b, kq = r.q.tapk + raw_q;  // (REC)
 #pragma unroll
         for (int k = 0; k < kPX; k++) {
-            const uint32_t ixb = (uint32_t)((L.sx[k] >> 5) - b.x0), ixq = (uint32_t)((L.sx[k] >> 5) - q.x0);
-            ta_b[k] = __umul24((uint32_t)((L.sy[k] >> 5) - b.y0), pitch_b) + (ixb * 2u + ixb) + raw_b;
-            ta_q[k] = __umul24((uint32_t)((L.sy2[k] >> 5) - q.y0), pitch_q) + (ixq * 2u + ixq) + raw_q;
+            if constexpr (REC) {  // (mirror_rec_tap: the coordinates carry the rounding bias, the origins its image)
+                const uint32_t bx = ((uint32_t)L.sx[k] >> 5), x3 = bx * 2u + bx;
+                ta_b[k] = mad24_vsv((uint32_t)L.sy[k] >> 5, pitch_b, x3 + kb);
+                ta_q[k] = mad24_vsv((uint32_t)L.sy2[k] >> 5, pitch_q, x3 + kq);
+            } else {
+                const uint32_t ixb = (uint32_t)((L.sx[k] >> 5) - b.x0), ixq = (uint32_t)((L.sx[k] >> 5) - q.x0);
+                ta_b[k] = __umul24((uint32_t)((L.sy[k] >> 5) - b.y0), pitch_b) + (ixb * 2u + ixb) + raw_b;
+                ta_q[k] = __umul24((uint32_t)((L.sy2[k] >> 5) - q.y0), pitch_q) + (ixq * 2u + ixq) + raw_q;
+            }
             W_b[k] = blend_weights(L.sx[k], L.sy[k]);
             W_q[k] = blend_weights(L.sx[k], L.sy2[k]);
         }
@@ -323,27 +393,51 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(REST ? V1C_
     const uint32_t row_off = (uint32_t)t.x0 * 3u;
     const int jm = (int)(kb_mh >> 16) - t.j;
     const bool band_row = jm < dsz.dst_h;
+    // byte offset of row j of eye e's destination (j and the pitch are below 2^24)
+    auto drow = [&](int e, int j) {
+        return (REC ? mul24_vs((uint32_t)j, (uint32_t)U[e].dst_pitch) : __umul24((uint32_t)j, (uint32_t)U[e].dst_pitch)) + row_off;
+    };
     uint32_t pix[kPX];
     // ---- eye 0 ----
     wait_vm_barrier(nq);  // tile box
     gather_taps_raw(ta_b, W_b, pitch_b, pix);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");  // band box landed; every wave has sampled the tile box
-    raw_box_dma(b, mb, U[1].src, (uint32_t)U[1].src_pitch, lane, wave, raw_b);
-    store4<1>(U[0].dst + (__umul24((uint32_t)t.j, (uint32_t)U[0].dst_pitch) + row_off), pix, 0xFu, dst_rows_dword_aligned(U, 0));
+    request(1, 0);
+    store4<1>(U[0].dst + drow(0, t.j), pix, 0xFu, dst_rows_dword_aligned(U, 0));
     gather_taps_raw(ta_q, W_q, pitch_q, pix);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // every wave has sampled the band box
-    raw_box_dma(q, mq, U[1].src, (uint32_t)U[1].src_pitch, lane, wave, raw_q);
+    request(1, 1);
     if (band_row)
-        store4<1>(U[0].dst + (__umul24((uint32_t)jm, (uint32_t)U[0].dst_pitch) + row_off), pix, 0xFu, dst_rows_dword_aligned(U, 0));
+        store4<1>(U[0].dst + drow(0, jm), pix, 0xFu, dst_rows_dword_aligned(U, 0));
     // ---- eye 1 (behind its tile box: eye 0's tile store and its band's nq requests; the predicated band store is not counted) ----
     wait_vm_barrier(nq + 1);
     gather_taps_raw(ta_b, W_b, pitch_b, pix);
     wait_vm_barrier_imm<0>();
-    store4<1>(U[1].dst + (__umul24((uint32_t)t.j, (uint32_t)U[1].dst_pitch) + row_off), pix, 0xFu, dst_rows_dword_aligned(U, 1));
+    store4<1>(U[1].dst + drow(1, t.j), pix, 0xFu, dst_rows_dword_aligned(U, 1));
     gather_taps_raw(ta_q, W_q, pitch_q, pix);
     if (band_row)
-        store4<1>(U[1].dst + (__umul24((uint32_t)jm, (uint32_t)U[1].dst_pitch) + row_off), pix, 0xFu, dst_rows_dword_aligned(U, 1));
+        store4<1>(U[1].dst + drow(1, jm), pix, 0xFu, dst_rows_dword_aligned(U, 1));
 }
+
+// REST = 0: the plan's rest list is empty (C2: every tile pair fits) -- the instantiation without the general pair code, whose
+// registers (74 against 68 VGPRs, 94 against 66 SGPRs) and LDS (its cell buffers) otherwise set the occupancy of a launch that never
+// runs it: 7 instead of 6 workgroups per CU
+template <int VAR_W, int REST = 1>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(REST ? V1C_SEQ_WAVES : V1C_SEQ_WAVES + 1, 8))) void k_ray_lin3_pair_mirror_seq(V1C_MIRROR_HEAD, TileArgs a_)
+{
+    __shared__ __attribute__((aligned(16))) double tabw[kTabSlice * kRadialCoefs];
+    extern __shared__ __attribute__((aligned(16))) uint32_t dyn_box[];  // 2 raw boxes of a.kb KB (or the general code's cell buffers)
+    mirror_seq_tile<VAR_W, REST, 1>(pairs, tiles_x_magic, gx_rest, rows_strip, dst_wh, rowcol_tables, ctxp, kb_mh, tabw, dyn_box);
+}
+#ifdef V1C_TUNING  // (V1C_MIRROR_REC=0: `pairs` = the plain box pairs)
+template <int VAR_W, int REST = 1>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(REST ? V1C_SEQ_WAVES : V1C_SEQ_WAVES + 1, 8))) void k_ray_lin3_pair_mirror_seq_box(V1C_MIRROR_HEAD, TileArgs a_)
+{
+    __shared__ __attribute__((aligned(16))) double tabw[kTabSlice * kRadialCoefs];
+    extern __shared__ __attribute__((aligned(16))) uint32_t dyn_box[];
+    mirror_seq_tile<VAR_W, REST, 0>(pairs, tiles_x_magic, gx_rest, rows_strip, dst_wh, rowcol_tables, ctxp, kb_mh, tabw, dyn_box);
+}
+#endif
 
 // Rest list of the mirror launch; false when the plan cannot use it (geometry, or more remaining tiles than the
 // launch's first grid slice holds).
@@ -425,11 +519,22 @@ bool tile_mirror_rest(const void* host_boxes, const void* host_mboxes, const Geo
     return rest.size() <= (size_t)d.x * (TYh - 1) && rest.size() * 4 <= (size_t)d.x * d.y;
 }
 
+void tile_mirror_records(const void* host_boxes, const void* host_mboxes, size_t n_tiles, const Geom& g, int seq_kb, int one_kb, std::vector<char>& out)
+{
+    const TileBox* b = (const TileBox*)host_boxes;
+    const TileBox* q = (const TileBox*)host_mboxes;
+    out.resize(n_tiles * sizeof(MirrorRecWords));
+    for (size_t i = 0; i < n_tiles; i++) {
+        const MirrorRecWords w = mirror_rec_encode(b[i], q[i], seq_kb, one_kb, g.src_h, g.src_w);
+        std::memcpy(&out[i * sizeof(MirrorRecWords)], &w, sizeof(w));
+    }
+}
+
 // lu.n = 2: apply_lr's pair; 1 (raw_nwp > 0): a single image through the one-eye instantiation of the LDS-DMA kernel
 // seq_kb > 0 (pairs): k_ray_lin3_pair_mirror_seq, two box buffers of seq_kb KB, the eyes one after the other
 hipError_t launch_ray_lin3_pair_mirror(const KernelCtx& c, const KernelCtx* cdev, const LaunchUnits& lu, uint32_t* flags, const void* boxes,
                                        const void* mboxes, int half_dwords, int mirror_h, const uint32_t* rest_list, int n_rest, int raw_nwp,
-                                       hipStream_t stream, int seq_kb)
+                                       hipStream_t stream, int seq_kb, const void* recs)
 {
     const int n_eyes = lu.n;
     const dim3 full = tile_grid(c.g, 256, 1);
@@ -463,19 +568,42 @@ hipError_t launch_ray_lin3_pair_mirror(const KernelCtx& c, const KernelCtx* cdev
     // destination size, the base of the plan's row / column tables (= col_s: one buffer), the context, box KB | mirror row << 16
     const unsigned srows = strip_rows == 2u && 2u * full.x < ((full.x * raw_rows) >> 3) ? 2u : 0u;
     const unsigned rows_strip = raw_rows | srows << 16, dst_wh = (unsigned)c.g.dst_w | (unsigned)c.g.dst_h << 16;
+    // (`pairs` of the head: the plan's launch records -- MirrorRec, tile_device.hpp -- for the seq and one-eye kernels, the plain box pairs
+    // for their A/B partners of the tuning build)
+    const TileBox* head_pairs = (const TileBox*)recs;
 #define V1C_MIRROR_LAUNCH(KERNEL, GRID, LDS, RESTROWS)                                                                                    \
-    hipLaunchKernelGGL(KERNEL, GRID, block, LDS, stream, a.mboxes, a.tiles_x_magic, full.x | (unsigned)(RESTROWS) << 16, rows_strip, dst_wh, \
+    hipLaunchKernelGGL(KERNEL, GRID, block, LDS, stream, head_pairs, a.tiles_x_magic, full.x | (unsigned)(RESTROWS) << 16, rows_strip, dst_wh, \
                        a.col_s, a.ctx, (unsigned)a.kb | (unsigned)a.mirror_h << 16, a)
+    [[maybe_unused]] bool rec_off = false;
+#ifdef V1C_TUNING
+    static const bool rec_off_env = [] {  // V1C_MIRROR_REC=0 (A/B): the prologue that decodes the box pair in every wave
+        const char* e = tuning_env("V1C_MIRROR_REC");
+        return e && e[0] == '0';
+    }();
+    rec_off = rec_off_env;
+#endif
     if (seq_kb > 0 && n_eyes == 2) {  // the eyes one after the other: two buffers of seq_kb KB (rest list made for that size)
         static const bool norest_off = [] {  // V1C_SEQ_NOREST=0 (A/B): the instantiation with the general pair code for every plan
             const char* e = tuning_env("V1C_SEQ_NOREST");
             return e && e[0] == '0';
         }();
         a.kb = seq_kb;
+        if (!rec_off && recs == nullptr)
+            return hipErrorInvalidValue;
         if (n_rest == 0 && !norest_off) {  // nothing for the general pair code: the instantiation (and the LDS) without it
             const dim3 rgrid(full.x, raw_rows, 1);
             const size_t slds = (size_t)2 * 1024 * (size_t)seq_kb + 16;
             a.rest_rows = 0;
+#ifdef V1C_TUNING
+            if (rec_off) {
+                head_pairs = a.mboxes;
+                if (c.ray.var_is_w)
+                    V1C_MIRROR_LAUNCH((k_ray_lin3_pair_mirror_seq_box<1, 0>), rgrid, slds, 0u);
+                else
+                    V1C_MIRROR_LAUNCH((k_ray_lin3_pair_mirror_seq_box<0, 0>), rgrid, slds, 0u);
+                return hipGetLastError();
+            }
+#endif
             if (c.ray.var_is_w)
                 V1C_MIRROR_LAUNCH((k_ray_lin3_pair_mirror_seq<1, 0>), rgrid, slds, 0u);
             else
@@ -485,6 +613,16 @@ hipError_t launch_ray_lin3_pair_mirror(const KernelCtx& c, const KernelCtx* cdev
         const dim3 rgrid(full.x, raw_rows + rest_rows, 1);
         const size_t slds = std::max((size_t)half_dwords * 8 + 16, (size_t)2 * 1024 * (size_t)seq_kb);
         a.rest_rows = rest_rows;
+#ifdef V1C_TUNING
+        if (rec_off) {
+            head_pairs = a.mboxes;
+            if (c.ray.var_is_w)
+                V1C_MIRROR_LAUNCH((k_ray_lin3_pair_mirror_seq_box<1>), rgrid, slds, rest_rows);
+            else
+                V1C_MIRROR_LAUNCH((k_ray_lin3_pair_mirror_seq_box<0>), rgrid, slds, rest_rows);
+            return hipGetLastError();
+        }
+#endif
         if (c.ray.var_is_w)
             V1C_MIRROR_LAUNCH((k_ray_lin3_pair_mirror_seq<1>), rgrid, slds, rest_rows);
         else
@@ -496,6 +634,18 @@ hipError_t launch_ray_lin3_pair_mirror(const KernelCtx& c, const KernelCtx* cdev
         // two boxes; the general pair code serves one unit from one cell buffer
         const size_t lds = std::max((size_t)half_dwords * 4 + 16, (size_t)2 * 1024 * (size_t)raw_nwp);
         a.kb = raw_nwp, a.rest_rows = rest_rows;
+        if (!rec_off && recs == nullptr)
+            return hipErrorInvalidValue;
+#ifdef V1C_TUNING
+        if (rec_off) {
+            head_pairs = a.mboxes;
+            if (c.ray.var_is_w)
+                V1C_MIRROR_LAUNCH((k_ray_lin3_pair_mirror_box_raw<1>), rgrid, lds, rest_rows);
+            else
+                V1C_MIRROR_LAUNCH((k_ray_lin3_pair_mirror_box_raw<0>), rgrid, lds, rest_rows);
+            return hipGetLastError();
+        }
+#endif
         if (c.ray.var_is_w)
             V1C_MIRROR_LAUNCH((k_ray_lin3_pair_mirror_raw<1, 1>), rgrid, lds, rest_rows);
         else
@@ -520,6 +670,7 @@ hipError_t launch_ray_lin3_pair_mirror(const KernelCtx& c, const KernelCtx* cdev
         if (skip == 2)
             rgrid.y = rest_rows;
         const unsigned rr = skip == 1 ? 0u : rest_rows;
+        head_pairs = a.mboxes;
         if (c.ray.var_is_w)
             V1C_MIRROR_LAUNCH((k_ray_lin3_pair_mirror_raw<1, 2>), rgrid, lds, rr);
         else

@@ -239,7 +239,8 @@ struct v1c_plan {
     // apply_lr pairs of unrotated chains: boxes of the bands that mirror the tiles about the equator and the tiles
     // the mirror launch leaves to the pair kernel (k_ray_lin3_pair_mirror); mirror_boxes == nullptr: not used
     void* mirror_boxes = nullptr;
-    const void* mirror_pairs = nullptr;  // (tile box, band box) interleaved, 64 bytes per tile: what the LDS-DMA mirror kernels read (one scalar load)
+    const void* mirror_recs = nullptr;   // the same slots as launch records (tile_device.hpp: MirrorRec): what the seq / one-eye kernels read
+    const void* mirror_pairs = nullptr;  // tuning build: (tile box, band box) interleaved, 64 bytes per tile, for the kernels' A/B partners
     const uint32_t* mirror_rest = nullptr;
     int n_mirror_rest = 0;
     int cn_kb = 0;                           // > 0: grayscale / BGRA bilinear through k_ray_lin_cn with box buffers of so many KB
@@ -800,6 +801,7 @@ extern "C" int v1c_plan_create_ex(v1c_plan** out, int device, const v1c_chain* c
                                 return rc;
                             }
                             p->mirror_boxes = mbx, p->n_mirror_rest = (int)mrest.size(), p->mirror_h = g.dst_h;
+#ifdef V1C_TUNING  // (the plain box pairs: what the A/B partners of the record-reading kernels load)
                             {
                                 std::vector<char> pairs(2 * hb.size());
                                 for (size_t i = 0; i < hb.size() / 32; i++) {
@@ -812,6 +814,17 @@ extern "C" int v1c_plan_create_ex(v1c_plan** out, int device, const v1c_chain* c
                                     return rc;
                                 }
                                 p->mirror_pairs = dp;
+                            }
+#endif
+                            if (p->mirror_raw_nwp > 0) {  // the launch records of the seq / one-eye kernels: their prologue, done once
+                                std::vector<char> recs;
+                                tile_mirror_records(hb.data(), hm.data(), hb.size() / 32, g, p->mirror_seq_kb, p->mirror_raw_nwp, recs);
+                                const char* dr = nullptr;
+                                if ((rc = upload(p, recs, &dr))) {
+                                    v1c_plan_destroy(p);
+                                    return rc;
+                                }
+                                p->mirror_recs = dr;
                             }
                             std::vector<uint32_t> mrest1;
                             if (p->mirror_raw_nwp > 0 && tile_mirror_rest(hb.data(), hm.data(), g, p->half_dwords, g.dst_h, mrest1, p->mirror_raw_nwp, true, 1)) {
@@ -1150,7 +1163,7 @@ extern "C" int v1c_plan_run(v1c_plan* p, void* stream, const v1c_unit* units, in
             HIP_TRY(launch_ray_lin3_pair_mirror(p->ctx, p->ctx_dev, lu, flags, p->tile_boxes, p->mirror_raw_nwp > 0 ? p->mirror_pairs : p->mirror_boxes,
                                                 p->half_dwords, p->mirror_h,
                                                 n == 1 ? p->mirror_rest1 : p->mirror_rest, n == 1 ? p->n_mirror_rest1 : p->n_mirror_rest,
-                                                p->mirror_raw_nwp, st, p->mirror_seq_kb));
+                                                p->mirror_raw_nwp, st, p->mirror_seq_kb, p->mirror_recs));
         } else if (d.fast && p->ctx.g.cn != 3) {
             // grayscale / BGRA: k_ray_lin_cn (one table entry per lane; plan-time boxes for the plan's own rotation, boxes reduced in the
             // kernel -- one unit per workgroup, a 12 KB buffer -- for units that override it)

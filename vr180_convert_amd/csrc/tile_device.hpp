@@ -373,7 +373,7 @@ __device__ __forceinline__ void load_rowcol(const Tables& P, int xc, int jc, Row
 // (1024 p + 512) >> 10 == p in the border-aware sampler, whose other three taps -- pixels or border values -- carry weight 0, and whose
 // top-left tap follows borderInterpolate like remapNearest's).  The rounded pixel lies inside the bilinear footprint of the same
 // coordinate, so boxes computed with NN = 1 (k_tile_boxes) bound it.
-template <int VAR_W, int ROT, int K, int OWN, int INTERIOR, int MPOLY, int MIRROR = 0, int NN = 0, typename TabPtr>
+template <int VAR_W, int ROT, int K, int OWN, int INTERIOR, int MPOLY, int MIRROR = 0, int NN = 0, int BIASED = 0, typename TabPtr>
 // `rot`: the rotation that applies (ROT != 0): the unit's own record -- the host stores the EFFECTIVE matrix there, the unit's override
 // or the chain's composed rotation (plan.hip: fill_unit) -- or c.ray.rot (k_tile_boxes)
 // `ext` (K = 4 / 8, BGR, BORDER_CONSTANT: kxk_ext()): a pixel counts as `inside` when its K x K footprint OVERLAPS the source instead of
@@ -536,10 +536,13 @@ __device__ __forceinline__ void lane_coords(ctx_cref c, rot_cptr rot, const RowC
                 L.sy[k] = (__float_as_int(ay * 0.03125f + 12582912.0f) - 0x4B400000) * 32;
                 continue;
             }
-            L.sx[k] = __float_as_int(ax + 12582912.0f) - 0x4B400000;
-            L.sy[k] = __float_as_int(ay + 12582912.0f) - 0x4B400000;
+            // BIASED (INTERIOR = 1, bilinear): the trick's raw bits, coordinate + kRoundBias -- the consumer's box origin carries the
+            // bias (MirrorRecBox::tapk) and the fractions are its low five bits either way
+            constexpr int bias = BIASED ? 0 : 0x4B400000;
+            L.sx[k] = __float_as_int(ax + 12582912.0f) - bias;
+            L.sy[k] = __float_as_int(ay + 12582912.0f) - bias;
             if (MIRROR && !ROT)
-                L.sy2[k] = __float_as_int((float)fma(G[k], -ky, cy32) + 12582912.0f) - 0x4B400000;
+                L.sy2[k] = __float_as_int((float)fma(G[k], -ky, cy32) + 12582912.0f) - bias;
             continue;
         }
         // flagged intervals carry NaN coefficients; |32 x| < 2^30 keeps the int conversion exact
@@ -2000,6 +2003,166 @@ __device__ __forceinline__ int raw_box_dma(const TileBox& b, const RawLanes& m, 
     return n;
 }
 
+// ---- the pair mirror kernel's launch record: what a tile pair's prologue derives from (plan, tile) alone, derived once per plan ----
+// Every wave of k_ray_lin3_pair_mirror_seq used to decode two TileBox records, test mirror_raw_fit, turn both cpr into units per row,
+// rows per pass and -- by an fp32 reciprocal -- its lanes' (row, unit) of a pass, and rebase every tap coordinate on the box origin:
+// the same numbers for every frame a plan serves.  plan.hip builds one 64-byte MirrorRecWords per tile pair from the boxes it has
+// downloaded anyway (mirror_rec_encode: the expressions the kernel used, on the host); the kernel reads it with the one scalar load
+// that fetched the box pair.  Only what belongs to the call stays in the kernel: source pointers and pitches.
+//   magic   ceil(2^16 / upr): floor(l / upr) == (l * magic) >> 16 for every lane l < 64 and upr <= 64 (l * (magic * upr - 2^16) <
+//           64 * 64 < 2^16); replaces raw_lanes_upr's reciprocal.
+//   tapk    the box origin of the tap addresses, biased: the coordinates stay the raw bits of the 1.5 * 2^23 rounding trick
+//           (lane_coords<..., BIASED = 1>: by = sy + 0x4B400000), and the LDS byte address of a pixel's first tap,
+//           ((sy >> 5) - y0) * lpitch + 3 * ((sx >> 5) - x0), is  mul24(by >> 5, lpitch) + 3 * (bx >> 5) + tapk  modulo 2^32 with
+//           tapk = -((y0 + 0x5A0000) * lpitch + 3 * (x0 + 0x25A0000)):  by >> 5 == (sy >> 5) + 0x25A0000 (the bias has no low five
+//           bits) and a 24-bit multiply sees its low 24 bits, (sy >> 5) + 0x5A0000 (sy >> 5 < 2^15).  by & 31 == sy & 31 likewise.
+constexpr uint32_t kRoundBias = 0x4B400000u;  // the bits of 1.5 * 2^23
+constexpr uint32_t kMirrorRecMpoly = 1u, kMirrorRecFitSeq = 2u, kMirrorRecFitOne = 4u;
+struct MirrorRecBox {
+    int y0, x3;       // first row; byte offset of the first column (3 x0)
+    int nrows, last0;  // rows; first row of the last pass (nrows - min(R, nrows))
+    int upr, R, nact;  // units per row, rows per pass, lanes with a unit in a pass (min(R, nrows) * upr)
+    uint32_t magic, lpitch, tapk;
+};
+struct MirrorRec {
+    MirrorRecBox b, q;
+    int idx0, nidx;   // the tile's table slice
+    uint32_t flags;   // kMirrorRecMpoly: evaluate the polynomial in m; kMirrorRecFitSeq / FitOne: mirror_raw_fit(b, q, seq_kb / one_kb) == 1
+};
+struct MirrorRecWords {
+    uint32_t w[16];
+};
+static_assert(sizeof(MirrorRecWords) == 2 * sizeof(TileBox), "one record per (tile box, band box) slot");
+
+// low 32 bits of the product of the operands' low 24 bits: what v_mul_u32_u24 computes
+__host__ __device__ inline uint32_t mul24_lo(uint32_t a, uint32_t b)
+{
+    return (uint32_t)((uint64_t)(a & 0xFFFFFFu) * (uint64_t)(b & 0xFFFFFFu));
+}
+__host__ __device__ inline uint32_t mirror_rec_lane_row(uint32_t lane, uint32_t magic)
+{
+    return mul24_lo(lane, magic) >> 16;
+}
+// LDS byte offset (from the box buffer) of the first tap of a pixel with biased coordinate bits (bx, by)
+__host__ __device__ inline uint32_t mirror_rec_tap(uint32_t bx, uint32_t by, uint32_t lpitch, uint32_t tapk)
+{
+    return mul24_lo(by >> 5, lpitch) + (bx >> 5) * 3u + tapk;
+}
+__host__ __device__ inline bool mirror_rec_box(const TileBox& t, MirrorRecBox& r, uint32_t (&w)[5])
+{
+    const bool ok = t.cpr > 0 && t.cpr <= kMaxCpr && t.nrows >= 0 && t.nrows < 2048 && t.x0 >= 0 && t.y0 >= 0 && t.x0 < 32768 && t.y0 < 32768;
+    r = MirrorRecBox{0, 0, 0, 0, 1, 1, 0, 65536u, 16u, 0u};
+    if (ok) {
+        r.upr = raw_units_per_row(t.cpr);
+        r.R = 64 / r.upr;
+        r.y0 = t.y0, r.x3 = 3 * t.x0, r.nrows = t.nrows;
+        const int rows = r.R < t.nrows ? r.R : t.nrows;
+        r.last0 = t.nrows - rows, r.nact = rows * r.upr;
+        r.magic = (65536u + (uint32_t)r.upr - 1u) / (uint32_t)r.upr;
+        r.lpitch = (uint32_t)r.upr * 16u;
+        r.tapk = 0u - (((uint32_t)t.y0 + (0xFFFFFFu & (kRoundBias >> 5))) * r.lpitch + 3u * ((uint32_t)t.x0 + (kRoundBias >> 5)));
+    }
+    w[0] = (uint32_t)r.y0 | (uint32_t)r.nrows << 16;
+    w[1] = (uint32_t)r.x3 | (uint32_t)r.last0 << 20;
+    w[2] = (uint32_t)r.upr | (uint32_t)r.R << 8 | (uint32_t)r.nact << 16;
+    w[3] = r.magic;
+    w[4] = r.tapk;
+    return ok;
+}
+__host__ __device__ inline MirrorRecBox mirror_rec_unbox(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4)
+{
+    MirrorRecBox r;
+    r.y0 = (int)(w0 & 0xffffu), r.nrows = (int)(w0 >> 16);
+    r.x3 = (int)(w1 & 0xfffffu), r.last0 = (int)(w1 >> 20);
+    r.upr = (int)(w2 & 0xffu), r.R = (int)((w2 >> 8) & 0xffu), r.nact = (int)(w2 >> 16);
+    r.magic = w3, r.lpitch = (w2 & 0xffu) * 16u, r.tapk = w4;
+    return r;
+}
+// `seq_kb`, `one_kb`: the box buffers of k_ray_lin3_pair_mirror_seq and of the one-eye k_ray_lin3_pair_mirror_raw for this plan (0: the
+// plan does not launch that kernel) -- the fit verdicts are the plan's, like the rest lists
+__host__ __device__ inline MirrorRecWords mirror_rec_encode(const TileBox& b, const TileBox& q, int seq_kb, int one_kb, int src_h, int src_w)
+{
+    MirrorRecWords o;
+    MirrorRecBox rb, rq;
+    uint32_t wb[5], wq[5];
+    const bool okb = mirror_rec_box(b, rb, wb), okq = mirror_rec_box(q, rq, wq);
+    for (int k = 0; k < 5; k++)
+        o.w[k] = wb[k], o.w[5 + k] = wq[k];
+    const bool ok = okb && okq && b.idx0 >= 0;
+    const bool fit_seq = ok && seq_kb > 0 && mirror_raw_fit(b, q, seq_kb, src_h, src_w) == 1;
+    const bool fit_one = ok && one_kb > 0 && mirror_raw_fit(b, q, one_kb, src_h, src_w) == 1;
+    const bool fit = fit_seq || fit_one;
+    o.w[10] = fit ? (uint32_t)b.idx0 : 0u;
+    o.w[11] = (fit ? (uint32_t)b.nidx : 1u) |
+              (((b.interior & 2) ? kMirrorRecMpoly : 0u) | (fit_seq ? kMirrorRecFitSeq : 0u) | (fit_one ? kMirrorRecFitOne : 0u)) << 16;
+    o.w[12] = o.w[13] = o.w[14] = o.w[15] = 0u;
+    return o;
+}
+__host__ __device__ inline MirrorRec mirror_rec_decode(const MirrorRecWords& v)
+{
+    MirrorRec r;
+    r.b = mirror_rec_unbox(v.w[0], v.w[1], v.w[2], v.w[3], v.w[4]);
+    r.q = mirror_rec_unbox(v.w[5], v.w[6], v.w[7], v.w[8], v.w[9]);
+    r.idx0 = (int)v.w[10], r.nidx = (int)(v.w[11] & 0xffffu), r.flags = v.w[11] >> 16;
+    return r;
+}
+__device__ __forceinline__ MirrorRec load_mirror_rec(const TileBox* pairs, int tile)
+{
+    typedef uint32_t __attribute__((ext_vector_type(16))) u32x16;
+    const u32x16 v = *(const V1C_CONST u32x16*)(pairs + 2 * __builtin_amdgcn_readfirstlane(tile));
+    MirrorRecWords o;
+#pragma unroll
+    for (int k = 0; k < 16; k++)
+        o.w[k] = v[k];
+    return mirror_rec_decode(o);
+}
+
+// v_mul_u32_u24 / v_mad_u32_u24 with a scalar factor, by hand (the compiler picks the quarter-rate v_mul_lo_u32 for it: raw_box_dma)
+__device__ __forceinline__ uint32_t mul24_vs(uint32_t v, uint32_t s)
+{
+    uint32_t r;
+    asm("v_mul_u32_u24 %0, %1, %2" : "=v"(r) : "v"(v), "s"(s));
+    return r;
+}
+__device__ __forceinline__ uint32_t mad24_vsv(uint32_t v, uint32_t s, uint32_t add)
+{
+    uint32_t r;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(v), "s"(s), "v"(add));
+    return r;
+}
+
+// raw_lanes / raw_box_dma from the record: the same passes, the same requests
+__device__ __forceinline__ RawLanes rec_lanes(const MirrorRecBox& r, int lane)
+{
+    RawLanes m;
+    m.upr = r.upr, m.R = r.R;
+    m.row_l = mul24_vs((uint32_t)lane, r.magic) >> 16;
+    m.col16 = ((uint32_t)lane - mul24_vs(m.row_l, (uint32_t)r.upr)) * 16u;
+    return m;
+}
+__device__ __forceinline__ int rec_box_dma(const MirrorRecBox& r, const RawLanes& m, const uint8_t* __restrict__ src, uint32_t spitch, int lane,
+                                            int wave, uint32_t lds_box)
+{
+    const uint32_t sp = (uint32_t)__builtin_amdgcn_readfirstlane((int)spitch);
+    const uint32_t voff = mul24_vs(m.row_l, sp) + m.col16;
+    const bool active = lane < r.nact;
+    const uint64_t org = (uint64_t)(uintptr_t)src + (uint64_t)((uint32_t)r.y0 * sp + (uint32_t)r.x3);
+    int n = 0;
+    for (int r0 = wave * r.R; r0 < r.nrows; r0 += 4 * r.R) {  // wave-uniform
+        const int rs = min(r0, r.last0);
+        const uint64_t base = org + (uint64_t)((uint32_t)rs * sp);
+        const uint32_t m0v = lds_box + (uint32_t)rs * r.lpitch;
+        uint32_t m0_saved;  // (the statement of raw_box_dma: see there)
+        if (active)
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 2\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                         : "=&s"(m0_saved)
+                         : "v"(voff), "s"(base), "s"(m0v)
+                         : "memory");
+        n++;
+    }
+    return n;
+}
+
 // s_waitcnt vmcnt(n) + s_barrier for a wave-uniform n; no fence: see the kernels.  The count is an immediate, so n selects one of
 // 21 sixteen-byte blocks (s_waitcnt | s_barrier | s_branch end | pad) by a computed jump: 6 scalar instructions and two jumps.
 // (As a switch the compiler structurised the 21 cases -- each holds a convergent barrier -- into a cascade of flag tests: ~30
@@ -2086,6 +2249,22 @@ __device__ __forceinline__ void gather_one_raw(const TileBox& b, uint32_t raw, c
         const uint32_t a0 = r0[0], a1 = r0[1], a2 = r0[2], b0 = r1[0], b1 = r1[1], b2 = r1[2];
         pix[k] = blend3<3>(__builtin_amdgcn_alignbyte(a1, a0, a), __builtin_amdgcn_alignbyte(a2, a1, a), __builtin_amdgcn_alignbyte(b1, b0, a),
                            __builtin_amdgcn_alignbyte(b2, b1, a), blend_weights(sx[k], sy[k]));
+    }
+}
+
+// ... from the launch record, the coordinates biased (mirror_rec_tap)
+__device__ __forceinline__ void gather_one_rec(const MirrorRecBox& r, uint32_t raw, const int (&bx)[kPX], const int (&by)[kPX], uint32_t (&pix)[kPX])
+{
+    const uint32_t kb = r.tapk + raw;
+#pragma unroll
+    for (int k = 0; k < kPX; k++) {
+        const uint32_t ix = (uint32_t)bx[k] >> 5;
+        const uint32_t a = mad24_vsv((uint32_t)by[k] >> 5, r.lpitch, ix * 2u + ix + kb);
+        const uint32_t d = a & ~3u;
+        const lds_u32_ptr r0 = (lds_u32_ptr)(uintptr_t)d, r1 = (lds_u32_ptr)(uintptr_t)(d + r.lpitch);
+        const uint32_t a0 = r0[0], a1 = r0[1], a2 = r0[2], b0 = r1[0], b1 = r1[1], b2 = r1[2];
+        pix[k] = blend3<3>(__builtin_amdgcn_alignbyte(a1, a0, a), __builtin_amdgcn_alignbyte(a2, a1, a), __builtin_amdgcn_alignbyte(b1, b0, a),
+                           __builtin_amdgcn_alignbyte(b2, b1, a), blend_weights(bx[k], by[k]));
     }
 }
 
