@@ -408,6 +408,51 @@ int v1c_fit_circle(int device, void* stream, const void* img, int h, int w, int6
                    const v1c_circle_params* params, void* workspace, double* out_host8, v1c_circle_point* points_out,
                    int32_t capacity, int32_t* n_points_out);
 
+/* ---- the colours of one eye matched to the other's (INTEGRATION.md section 12 states the contract; tests/colormatch_ref.py restates
+ * it).  Two (h, w, cn) 8-bit device images of one shape, cn 1 / 3 / 4, each with its own row pitch in BYTES.  MASK: a position counts
+ * when the maximum over the colour channels (the first three of four, or the only one) lies in [lo, hi] in BOTH eyes; n positions
+ * count.  HISTOGRAMS: h[eye][c][v], uint32, eye 0 = left, over the counted positions.  The TARGET is the eye that is not the
+ * reference; T, R are the target's and the reference's counts of one channel, CT, CR their running sums.
+ * MODE HISTOGRAM: knots (v, min{u : 2 CR[u] >= CT[v-1] + CT[v]}) at every populated bin v of T, (0, 0) and (255, 255) where bin 0 /
+ * 255 is not populated; between neighbouring knots (a, ma), (b, mb): m = ma + ((v-a)(mb-ma) 2 + (b-a)) / (2 (b-a)), floored; the entry
+ * is clamp(clamp(m, v - max_shift, v + max_shift), 0, 255).  MODE GAIN: sT, sR the sums of v T[v], v R[v] (int64),
+ * g = clamp((sR 65536 + sT / 2) / sT, 16384, 262144), the entry min(255, (v g + 32768) >> 16).
+ * REPORT, 20 int32: status, n, then per colour channel c at 2 + 5 c: first and last populated bin of the left eye, of the right eye
+ * (-1: none, or a channel the image lacks), g (0 outside gain mode and where sT is 0); two spare words, 0.  status: 0, or 1
+ * (n < min_pixels), 2 (gain mode, sT == 0 in a channel; 1 goes first).  A non-zero status gives identity tables.  A one-channel
+ * image's second and third table are the identity.                                                                              */
+#define V1C_CM_MODE_HISTOGRAM   0
+#define V1C_CM_MODE_GAIN        1
+#define V1C_CM_REFERENCE_LEFT   0
+#define V1C_CM_REFERENCE_RIGHT  1
+
+typedef struct v1c_color_match_params {
+    int32_t mode;           /* V1C_CM_MODE_* [HISTOGRAM]                                                                         */
+    int32_t reference;      /* V1C_CM_REFERENCE_* [LEFT]: the eye that stays as it is                                            */
+    int32_t lo, hi;         /* the mask, 0 <= lo <= hi <= 255 [10, 254]                                                          */
+    int32_t max_shift;      /* 0..255 [64]                                                                                       */
+    int32_t min_pixels;     /* >= 0 [1024]                                                                                       */
+} v1c_color_match_params;
+
+/* Bytes of device memory v1c_color_match_luts_async needs as its workspace (the histograms: 2 x 3 x 256 uint32).  Host-only.       */
+uint64_t v1c_color_match_workspace(void);
+
+/* Builds the three 256-entry tables that map the target eye onto the reference eye, on `stream`: the workspace zeroed, two launches,
+ * no allocation, no copy to the host, no synchronisation -- it can be captured into a graph, and a replay starts from a zeroed
+ * workspace.  `workspace`: device memory of v1c_color_match_workspace() bytes, 4-byte aligned, the caller's, in use until the work has
+ * run; it holds the histograms afterwards.  luts_dev: 3 x 256 bytes, report_dev: 20 int32, both on the device.  params NULL: the
+ * defaults.  Neither eye is written.  V1C_E_INVALID before any device call for NULL pointers, cn, non-positive sizes or
+ * h * w >= 2^31, a pitch below a row's bytes, alignment, parameters out of range.                                                 */
+int v1c_color_match_luts_async(int device, void* stream, const void* left, int64_t left_pitch, const void* right, int64_t right_pitch,
+                               int h, int w, int cn, const v1c_color_match_params* params, void* workspace, uint8_t* luts_dev,
+                               int32_t* report_dev);
+
+/* dst[c] = luts[c][src[c]] on the colour channels of an (h, w, cn) 8-bit device image, a fourth channel copied; one launch on `stream`.
+ * dst may be src (in place) or another image that does not overlap it, with its own pitch.  The tables may come from another pair of
+ * the same shoot.  V1C_E_INVALID as above.                                                                                        */
+int v1c_apply_luts_async(int device, void* stream, const void* src, int64_t src_pitch, void* dst, int64_t dst_pitch, int h, int w, int cn,
+                         const uint8_t* luts_dev);
+
 /* ---- PNG encoding of a device image (INTEGRATION.md section 6 states the stream; tests/png_ref.py restates it) ------------------
  * The image's filtered scanlines, cut into bands of band_rows rows, every band deflated from an empty window as ONE dynamic Huffman
  * block of literals and distance-1 matches (zlib's Z_RLE class) closed by an empty stored block, or as stored blocks where that is

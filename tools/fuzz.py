@@ -7,7 +7,7 @@ and destination views (dword-aligned or not), per-unit rotations, apply_lr pairs
 (v1c_remap_lut) on random float32 maps sprinkled with NaN, infinities, 2^15 / 2^26 / 2^31-scale values and ties of the 1/32 grid.
 
     python3 tools/fuzz.py [--seconds 300] [--seed 1] [--big 0.15] [--lut 0.15] [--hot 0.3] [--gen2 0] [--api 0.1] [--auto 0.06] [--fused 0.06] [--log gpurun_out/fuzz.log]
-                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--jpegprog 0] [--jpegxc 0] [--jpegxf 0] [--jpegdmg 0] [--jpegodd 0] [--circle 0] [--cases N]
+                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--jpegprog 0] [--jpegxc 0] [--jpegxf 0] [--jpegdmg 0] [--jpegodd 0] [--circle 0] [--colormatch 0] [--cases N]
 
 --wide P: that share of the cases has uint16 or float32 pixels (k_remap_wide): the chain cases above -- same grammar, views, batches, pairs,
 per-unit rotations, graph replays and the same three masks, counted in the same counters -- and the LUT cases (v1c_remap_lut_ex, nothing left
@@ -38,7 +38,11 @@ segment of a small supported file (tests/jpgodd_cases.py), against the restateme
 (the summary line says how many were refused as predicted).  --circle P: that share goes through the image-circle fit
 (v1c_fit_circle: random discs, clips, wedges, noise, pixel types, channel counts, views and parameters) against tests/circle_ref.py --
 rim points, selection flags and counts equal, floats within 1e-9 px -- and, for a part of them, through apply() / apply_lr_tensors()
-with random off-centre center= values against oracle.remap of the host NumPy chain's map with those centres.  These shares come off
+with random off-centre center= values against oracle.remap of the host NumPy chain's map with those centres.  --colormatch P: that
+share goes through the colour match of two eyes (color_match_luts_tensor + apply_luts_tensor: random sizes with odd widths, channel
+counts, pitches, offsets, halves of a side-by-side buffer, modes, references, parameters off the defaults, in place and out of place,
+noise, flat frames, gradients and discs on black whose surrounds differ) against tests/colormatch_ref.py, byte for byte: histograms,
+tables, report, result and every byte of the buffer around the eyes.  These shares come off
 the top of the case draw: with all of them at 0 every earlier seed replays as it ran.
 
 Round 5 added to the grammar: hot shapes of the chains that left the interpreter (planar fisheye -> fisheye, is_latitude_y=False, a
@@ -1445,6 +1449,69 @@ def circle_case(rng, dev) -> tuple[str, int]:
     return desc, bad
 
 
+COLORMATCH = {"drawn": 0}
+
+
+def colormatch_case(rng, dev) -> tuple[str, int]:
+    """color_match_luts_tensor + apply_luts_tensor against tests/colormatch_ref.py, byte for byte: histograms, tables, report, the
+    result and every byte of the buffer around the eyes"""
+    import colormatch_cases as CC
+    import colormatch_ref as CMR
+    from vr180_convert_amd import colormatch
+
+    COLORMATCH["drawn"] += 1
+    h, w = (int(rng.integers(1, 200)), int(rng.integers(1, 300))) if rng.random() < 0.85 else (int(rng.integers(200, 900)), int(rng.integers(300, 1400)))
+    cn = int(rng.choice([1, 3, 4]))
+    kind = str(rng.choice(["noise", "flat", "gradient", "disc", "disc", "discs_apart", "black"]))
+    seed = int(rng.integers(0, 1 << 30))
+    if kind == "noise":
+        L = np.random.default_rng(seed).integers(0, 256, (h, w, cn), dtype=np.uint8)
+    elif kind == "flat":
+        L = np.full((h, w, cn), int(rng.integers(0, 256)), np.uint8)
+    elif kind == "gradient":
+        L = np.broadcast_to((np.arange(w) * 255 // max(1, w - 1)).astype(np.uint8)[None, :, None], (h, w, cn)).copy()
+    elif kind == "black":
+        L = np.zeros((h, w, cn), np.uint8)
+    else:
+        L = CC.noise_disc(h, w, cn, seed, lo=int(rng.integers(0, 40)), hi=int(rng.integers(60, 256)), cx=w * rng.uniform(0.3, 0.7),
+                          cy=h * rng.uniform(0.3, 0.7), r=min(h, w) * rng.uniform(0.2, 0.6))
+    how = str(rng.choice(["brighter", "affine", "gamma", "same", "other"]))
+    if how == "brighter":
+        Rr = CC.brighter(L)
+    elif how == "affine":
+        Rr = np.clip(L.astype(np.int32) * int(rng.integers(2, 9)) // 4 + int(rng.integers(-30, 30)), 0, 255).astype(np.uint8)
+    elif how == "gamma":
+        Rr = (255.0 * (L / 255.0) ** rng.uniform(0.5, 2.0)).astype(np.uint8)
+    elif how == "same":
+        Rr = L.copy()
+    else:
+        Rr = np.random.default_rng(seed + 1).integers(0, 256, (h, w, cn), dtype=np.uint8)
+    if kind == "discs_apart":  # the eyes' surrounds differ
+        Rr = np.roll(Rr, (int(rng.integers(-h // 3 - 1, h // 3 + 1)), int(rng.integers(-w // 3 - 1, w // 3 + 1))), axis=(0, 1))
+    kw: dict = dict(mode=str(rng.choice(["histogram", "gain"])), reference=str(rng.choice(["left", "right"])))
+    if rng.random() < 0.5:
+        lo = int(rng.integers(0, 120))
+        kw.update(lo=lo, hi=int(rng.integers(lo, 256)), max_shift=int(rng.choice([0, 1, 20, 64, 255])), min_pixels=int(rng.choice([0, 1, 100, 1024])))
+    layout = str(rng.choice(["separate", "padded", "sbs", "sbs_padded"]))
+    lay = dict(off=int(rng.integers(0, 17)))
+    if layout == "padded":
+        lay.update(pad_l=int(rng.integers(0, 40)), pad_r=int(rng.integers(0, 40)))
+    elif layout.startswith("sbs"):
+        lay.update(sbs=True, pad=int(rng.integers(0, 40)) if layout == "sbs_padded" else 0)
+    case = CC.carve(L, Rr, kw=kw, inplace=bool(rng.random() < 0.5), **lay)
+    desc = f"colormatch {kind}/{how} {h}x{w}x{cn} {layout} {lay} inplace {case.inplace} {kw}"
+    base_t = torch.from_numpy(case.base.copy()).to(dev)
+    left, right = (torch.as_strided(base_t, (h, w, cn), (p_, cn, 1), off) for off, p_ in (case.left, case.right))
+    ws = torch.full((2, 3, 256), -1, dtype=torch.int32, device=dev)
+    luts, report = colormatch.color_match_luts_tensor(left, right, workspace=ws, **kw)
+    tgt = right if case.target == "right" else left
+    out = colormatch.apply_luts_tensor(tgt, luts, out=tgt if case.inplace else None)
+    wres, wluts, wrep, whist = CC.reference_of(case)
+    bad = int((ws.cpu().numpy().view(np.uint32) != whist).sum()) + int((luts.cpu().numpy() != wluts).sum()) + int((report.cpu().numpy() != wrep).sum())
+    bad += int((out.cpu().numpy() != wres).sum()) + int((base_t.cpu().numpy() != CC.expected_base(case, wres)).sum())
+    return desc, bad
+
+
 def circle_remap_case(rng, dev) -> tuple[str, int]:
     h, w = int(rng.integers(24, 700)), int(rng.integers(24, 700))
     wo, ho = int(rng.integers(8, 600)), int(rng.integers(8, 600))
@@ -1642,6 +1709,7 @@ def main() -> int:
     ap.add_argument("--jpegdmg", type=float, default=0.0, help="share of cases through the device JPEG decoders with one random damage inside a scan, against the verdict of tests/jpgdmg_cases.py")
     ap.add_argument("--jpegodd", type=float, default=0.0, help="share of cases through the device JPEG decoders with a legal file of unusual structure or one damaged header, against tests/jpgodd_cases.py")
     ap.add_argument("--circle", type=float, default=0.0, help="share of cases through the image-circle fit (v1c_fit_circle) against circle_ref.fit, a part of them remaps with random off-centre center= against the oracle")
+    ap.add_argument("--colormatch", type=float, default=0.0, help="share of cases through the colour match of two eyes (color_match_luts_tensor, apply_luts_tensor) against colormatch_ref, byte for byte")
     ap.add_argument("--cases", type=int, default=None, help="stop after this many cases (before --seconds runs out)")
     ap.add_argument("--feat", type=float, default=0.0, help="share of cases through the feature pipeline (features.detect / features.match) against tests/feat_ref.py")
     ap.add_argument("--only", type=int, default=None, help="run only this case number (reproduce)")
@@ -1676,12 +1744,15 @@ def main() -> int:
             r_kind = rng.random()
             wide_chain = False
             counted = True
-            rest000 = 1.0 - a.circle
+            rest0000 = 1.0 - a.colormatch
+            rest000 = rest0000 - a.circle
             rest00 = rest000 - a.jpegodd
             rest0 = rest00 - a.jpegdmg
             rest = rest0 - a.jpegxf
             top = rest - a.jpegxc - a.jpegprog - a.jpegopt - a.jpegbatch - a.jpegdec
-            if r_kind >= rest000:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+            if r_kind >= rest0000:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+                desc, bad = colormatch_case(rng, dev)
+            elif r_kind >= rest000:
                 desc, bad = circle_case(rng, dev)
             elif r_kind >= rest00:
                 desc, bad = jpegodd_case(rng, dev)
@@ -1752,7 +1823,8 @@ def main() -> int:
            if DMG["drawn"] else "")
         + (f"; jpegodd cases: {ODD['drawn']} drawn, {ODD['legal']} legal files and {ODD['damage']} damaged headers, {ODD['refused']} of them refused as predicted"
            if ODD["drawn"] else "")
-        + (f"; circle cases: {CIRCLE['drawn']} drawn" if CIRCLE["drawn"] else ""))
+        + (f"; circle cases: {CIRCLE['drawn']} drawn" if CIRCLE["drawn"] else "")
+        + (f"; colormatch cases: {COLORMATCH['drawn']} drawn" if COLORMATCH["drawn"] else ""))
     say("kernel families of the chain cases' launch groups: " + ", ".join(f"{k} x{v}" for k, v in sorted(KINDS.items())))
     return 1 if n_bad else 0
 

@@ -29,6 +29,18 @@ from .jpeg_compose_device import (compose_regions, join_sbs_jpeg, normalize_orie
 from .sharding import remap_sharded
 from .circle import Circle, fit_circle, fit_circle_tensor
 
+_COLORMATCH = ("color_match_luts_tensor", "apply_luts_tensor", "match_eyes_tensors", "color_match_report", "ColorMatchReport")
+
+
+def __getattr__(name: str):
+    # colormatch.py is imported on first use: an apply_lr without match_colors= runs none of it
+    if name in _COLORMATCH:
+        from . import colormatch
+
+        return getattr(colormatch, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 __all__ = [
     "TransformerBase",
     "ZoomTransformer",
@@ -87,4 +99,10 @@ __all__ = [
     "fit_circle",
     "fit_circle_tensor",
     "Circle",
+    # the colours of one eye matched to the other's on the device (match_colors= / --match-colors)
+    "color_match_luts_tensor",
+    "apply_luts_tensor",
+    "match_eyes_tensors",
+    "color_match_report",
+    "ColorMatchReport",
 ]

@@ -31,6 +31,7 @@ SYMBOLS = [
     "v1c_jpeg_transcode_bound", "v1c_jpeg_transcode_check", "v1c_jpeg_header_xc", "v1c_jpeg_transcode",
     "v1c_jpeg_compose_bound", "v1c_jpeg_compose_check", "v1c_jpeg_header_xf", "v1c_jpeg_compose",
     "v1c_fit_circle_workspace", "v1c_fit_circle_async", "v1c_fit_circle",
+    "v1c_color_match_workspace", "v1c_color_match_luts_async", "v1c_apply_luts_async",
 ]
 
 
@@ -147,6 +148,13 @@ def lib() -> C.CDLL:
         L.v1c_fit_circle_workspace.restype = C.c_uint64
         L.v1c_fit_circle_async.argtypes = [i32, vp, vp, i32, i32, i64, i32, i32, vp, vp, vp]
         L.v1c_fit_circle.argtypes = [i32, vp, vp, i32, i32, i64, i32, i32, vp, vp, vp, vp, i32, vp]
+    except AttributeError:  # (an older build behind V1C_LIB)
+        pass
+    try:
+        L.v1c_color_match_workspace.argtypes = []
+        L.v1c_color_match_workspace.restype = C.c_uint64
+        L.v1c_color_match_luts_async.argtypes = [i32, vp, vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp]
+        L.v1c_apply_luts_async.argtypes = [i32, vp, vp, i64, vp, i64, i32, i32, i32, vp]
     except AttributeError:  # (an older build behind V1C_LIB)
         pass
     L.v1c_plan_run.argtypes = [vp, vp, C.POINTER(_abi.Unit), i32]

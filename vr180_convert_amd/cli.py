@@ -253,9 +253,19 @@ def lr(
     device_vr180: Annotated[bool, typer.Option("--device-vr180", help="Write a .jpg / .jpeg result as a Google VR180 photo: both eyes "
                                                                        "encoded on the GPU, the right eye embedded in the left eye's "
                                                                        "XMP (not with --merge)")] = False,
+    match_colors: Annotated[str, typer.Option("--match-colors", help="Match the colours of one eye to the other's on the GPU after the "
+                                                                      "remap: 'gain' (one factor per channel) or 'histogram' (the "
+                                                                      "distributions); 8-bit images; default: off")] = "",
+    match_reference: Annotated[str, typer.Option("--match-reference", help="With --match-colors: the eye of the result that stays as it "
+                                                                            "is, 'left' or 'right' (after --swap)")] = "left",
 ) -> None:
     """Remap a pair of fisheye images to a pair of SBS equirectangular images."""
     from .remapper import apply_lr
+
+    if match_colors not in ("", "gain", "histogram"):
+        raise typer.BadParameter(f"--match-colors {match_colors}: expected 'gain' or 'histogram'")
+    if match_reference not in ("left", "right"):
+        raise typer.BadParameter(f"--match-reference {match_reference}: expected 'left' or 'right'")
 
     r_earlier_l = autosearch_timestamp_calib_r_earlier_l
     if swap:
@@ -298,7 +308,8 @@ def lr(
              **({"device_jpeg": "vr180"} if device_vr180 else {"device_jpeg": "batch"} if device_jpeg_batch else {"device_jpeg": True} if device_jpeg else {}),
              **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}),
              **({"device_jpeg_optimize": True} if device_jpeg_optimize else {}),
-             **({"device_decode_progressive": True} if device_decode_progressive else {}))
+             **({"device_decode_progressive": True} if device_decode_progressive else {}),
+             **({"match_colors": match_colors, "match_reference": match_reference} if match_colors else {}))
 
 
 @app.command()

@@ -1015,6 +1015,8 @@ def apply_lr_tensors(
     radius: float | Literal["auto", "max"] = "auto",
     auto_radius_on_device: bool | None = None,
     center: Any = None,
+    match_colors: Literal["gain", "histogram"] | None = None,
+    match_reference: Literal["left", "right"] = "left",
 ) -> torch.Tensor:
     """Device-resident ``apply_lr`` (merge=False): both eyes are remapped by ONE launch straight
     into the halves of the ``(H, 2W, C)`` side-by-side tensor (remapper.py:460-484, 517-518).
@@ -1034,7 +1036,20 @@ def apply_lr_tensors(
     to 1/4 px (circle.py).  Eyes whose centres differ are remapped by a launch each.  ``"auto"`` needs the fitted centres on the host
     (the plan's tile boxes depend on them): NotImplementedError under stream capture and with ``auto_radius_on_device=True``; explicit
     centres work in both.  ``radius="fit"``: the fitted radius (``get_radius_smart``), positive; ``radius="auto"`` keeps its value,
-    sign included, whatever ``center``."""
+    sign included, whatever ``center``.
+
+    ``match_colors``: ``"gain"`` or ``"histogram"`` -- after the remap, the half that is not ``match_reference`` is rewritten in place so
+    that its colours match the other half's (colormatch.py; three more launches on the current stream, nothing synchronised, so it goes
+    into a graph capture with the remap).  uint8 eyes only: ValueError before anything is remapped.  None: nothing of it runs."""
+    if match_colors is not None:
+        _check_match_colors(match_colors, match_reference, left, right)
+        out = apply_lr_tensors(transformer, left, right, out=out, size_output=size_output, interpolation=interpolation,
+                               boarder_mode=boarder_mode, boarder_value=boarder_value, radius=radius,
+                               auto_radius_on_device=auto_radius_on_device, center=center)
+        from . import colormatch
+
+        colormatch.match_eyes_tensors(out[:, : size_output[0]], out[:, size_output[0]:], mode=match_colors, reference=match_reference)
+        return out
     w, h = size_output
     cn = left.shape[2]
     fits = None
@@ -1105,6 +1120,17 @@ def apply_lr_tensors(
     return out
 
 
+def _check_match_colors(match_colors: Any, match_reference: Any, left: Any, right: Any) -> None:
+    """the arguments of ``match_colors=``, before anything is remapped"""
+    if match_colors not in ("gain", "histogram"):
+        raise ValueError(f'match_colors must be None, "gain" or "histogram", not {match_colors!r}')
+    if match_reference not in ("left", "right"):
+        raise ValueError(f'match_reference must be "left" or "right", not {match_reference!r}')
+    for im in (left, right):
+        if str(im.dtype).replace("torch.", "") != "uint8":
+            raise ValueError(f"match_colors: uint8 images only, not {im.dtype} (wide pixels need a histogram of their own design)")
+
+
 def anaglyph_tensors(left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
     """``merge=True`` of apply_lr on the device (reference remapper.py:485-497): per-eye channel
     mean times a colour, summed, / 255 -- a float64 ``(H, W, 3)`` tensor like the reference's
@@ -1142,6 +1168,8 @@ def apply_lr(
     device_jpeg_optimize: bool = False,
     device_decode_progressive: bool = False,
     center: Any = None,
+    match_colors: Literal["gain", "histogram"] | None = None,
+    match_reference: Literal["left", "right"] = "left",
 ) -> None:
     """Apply transformer to a pair of images and save them side by side (reference
     remapper.py:406-520).  ``left_path == right_path`` means one file holding both eyes.
@@ -1162,7 +1190,11 @@ def apply_lr(
     host reader (``progressive=True`` of jpeg_decode_device.py).
     ``center``: as in ``apply_lr_tensors`` -- ``(cx, cy)``, a pair of them per eye, or ``"auto"``.  With one file holding both eyes the
     centres are in each HALF's own coordinates, and ``"auto"`` fits each half: the circles of a side-by-side fisheye frame are nowhere
-    near ``W // 2`` of their halves."""
+    near ``W // 2`` of their halves.
+    ``match_colors``, ``match_reference``: as in ``apply_lr_tensors`` -- the colours of one remapped eye matched to the other's on the
+    device, before the anaglyph of ``merge=True`` and before every writer.  ValueError for a pair that is not uint8, before anything is
+    remapped.  Where the result comes to the host anyway, a match that ended in a status (too few pixels in the mask) is logged as a
+    warning; the device writers leave the report on the device."""
     vr180 = isinstance(device_jpeg, str) and device_jpeg == "vr180"
     device_jpeg = True if vr180 else _device_jpeg_mode(device_jpeg)
     if vr180 and merge:
@@ -1184,11 +1216,14 @@ def apply_lr(
     left, right = _io.imread_many([left_path, right_path])  # (two files: decoded side by side, the codecs release the GIL)
     on_device = isinstance(left, torch.Tensor) and left.is_cuda
     dev = left.device if on_device else _device(device)
+    if match_colors is not None:
+        _check_match_colors(match_colors, match_reference, left, right)
     lt, rt = _to_device(left, dev), _to_device(right, dev)
     # "auto" radius: estimated on the host images when they are numpy (one row each)
     sbs = apply_lr_tensors(transformer, lt, rt, size_output=size_output, interpolation=interpolation,
                            boarder_mode=boarder_mode, boarder_value=boarder_value,
                            radius=_radius_for_pair(radius, transformer, left, right), center=center)
+    match_report = _match_sbs_colors(sbs, size_output[0], match_colors, match_reference) if match_colors is not None else None
     if merge and sbs.dtype != torch.uint8:
         # 16-bit / float32: the reference's own NumPy expression (remapper.py:485-497) on the host copy (the anaglyph kernel is 8-bit)
         w = size_output[0]
@@ -1229,9 +1264,26 @@ def apply_lr(
                 LOG.info(f"Saved to {Path(out_path).absolute()}")
                 return
         combine = sbs.cpu().numpy()
+    if match_report is not None:  # (the result is on the host: the report costs no further wait)
+        from . import colormatch
+
+        rep = colormatch.color_match_report(match_report)
+        if rep.status:
+            LOG.warning(f"match_colors: the eyes were left as they are: {colormatch.STATUS.get(rep.status, rep.status)} (n = {rep.n})")
     if out_path is not None:
         _io.imwrite(out_path, combine)
         LOG.info(f"Saved to {Path(out_path).absolute()}")
+
+
+def _match_sbs_colors(sbs: torch.Tensor, w: int, mode: str, reference: str) -> torch.Tensor:
+    """the halves of a side-by-side result matched in place (colormatch.py); returns the report record, left on the device"""
+    from . import colormatch
+
+    halves = (sbs[:, :w], sbs[:, w:])
+    luts, report = colormatch.color_match_luts_tensor(*halves, mode=mode, reference=reference)
+    target = halves[1] if reference == "left" else halves[0]
+    colormatch.apply_luts_tensor(target, luts, out=target)
+    return report
 
 
 def _radius_for_pair(radius, transformer, left, right):
