@@ -247,6 +247,7 @@ enum {
     V1C_LAUNCH_BATCH = 5,   /* BGR bilinear batches sharing a map: k_ray_lin3_batch_lean_raw (+ k_ray_lin3_tile for its rest tiles) */
     V1C_LAUNCH_ROT_PAIR = 6, /* BGR bilinear units with a rotation of their own: k_ray_lin3_rot_pair_raw */
     V1C_LAUNCH_WIDE = 7,    /* 16-bit / float32 pixels: k_remap_wide (plans of v1c_plan_create_ex with a wide depth) */
+    V1C_LAUNCH_CHROMA = 8,  /* BGR, one map per colour channel: k_remap_ca (plans of v1c_ca_plan_create; samples from global memory) */
     V1C_LAUNCH_FIXUP = 0x100
 };
 int v1c_plan_last_launch(const v1c_plan* plan);
@@ -779,6 +780,32 @@ int64_t v1c_jpeg_header_xf(const uint8_t* file, uint64_t size, int width, int he
  * captured.                                                                                                                       */
 int v1c_jpeg_compose(int device, void* stream, int nsources, const v1c_jpeg_xf_source* sources, int n, v1c_jpeg_xf_output* outputs,
                      uint32_t subseq_bits, v1c_jpeg_decode_report* reports);
+
+/* ---- lateral chromatic aberration: one map per colour channel of a BGR remap ---------------------------------------------------
+ * A lens magnifies red, green and blue by slightly different amounts; the correction is a radial rescaling of the source position
+ * per channel, i.e. three chains that differ in radial stages in front of Denormalize (chromatic.py: transformer *
+ * PolynomialScaler(coefs_c)).  A v1c_ca_plan takes the three lowered chains -- B, G, R, each as v1c_plan_create takes its one -- and
+ * remaps uint8 BGR units so that byte c of every output pixel is what a v1c_plan of chain c writes there (same sizes, interpolation,
+ * border mode and colour; under BORDER_TRANSPARENT a channel whose own footprint leaves the source keeps the destination's byte).
+ * The numerical contract above carries over.  When the chains agree in everything but the radial composite behind the rotation and
+ * every radial table is usable, the plan is FUSED: one ray direction per pixel, one table per distinct composite
+ * (v1c_ca_plan_path 1); otherwise three fp64 interpreters run per pixel (path 0).
+ *
+ * v1c_ca_plan_run: launch-only (no allocation, no synchronisation), graph-capturable; 16 units per launch, longer arrays in several
+ * launches; argument errors are reported before any device call; one plan may be run from several threads / streams (the ray pass,
+ * its tile-flag words and the fix-up pass keep stream order through an event).  Units may override the rotation as for v1c_plan_run
+ * when every chain has the same number (> 0) of rotate stages.
+ * v1c_ca_plan_get_map: the float32 map of one channel (0 B, 1 G, 2 R), as v1c_plan_get_map.
+ * v1c_ca_plan_last_launch: V1C_LAUNCH_CHROMA, | V1C_LAUNCH_FIXUP when a fix-up pass followed; -1 before the first run.            */
+typedef struct v1c_ca_plan v1c_ca_plan;
+int v1c_ca_plan_create(v1c_ca_plan** out, int device, const v1c_chain chains[3] /* B, G, R */, int src_h, int src_w, int dst_h,
+                       int dst_w, int interp, int border_mode, const uint8_t border_val[4]);
+int v1c_ca_plan_run(v1c_ca_plan* plan, void* stream, const v1c_unit* units, int n_units);
+int v1c_ca_plan_get_map(v1c_ca_plan* plan, void* stream, int channel, float* xmap, float* ymap, int64_t map_pitch,
+                        const double* rot_or_null);
+int v1c_ca_plan_path(const v1c_ca_plan* plan);        /* 0 literal, 1 fused ray */
+int v1c_ca_plan_last_launch(const v1c_ca_plan* plan);
+int v1c_ca_plan_destroy(v1c_ca_plan* plan);
 
 #ifdef __cplusplus
 }

@@ -1540,6 +1540,76 @@ def circle_remap_case(rng, dev) -> tuple[str, int]:
 
 
 CIRCLE = {"drawn": 0}
+CHROMA = {"drawn": 0, "fixup": 0, "literal": 0}
+
+
+def chroma_case(rng, dev) -> tuple[str, int]:
+    """--chroma: a remap case with a random ChromaticAberration (chromatic.py) against the per-channel oracle composition -- channel c
+    of the result is channel c of the oracle's image for the chain with that channel's polynomial appended.  Coefficients within 2 %
+    linear and 2 % cubic of the identity, now and then a constant term (the table of that channel then loses its centre: fix-up
+    passes).  The ill-conditioned pixels and float32 rounding ties of each channel's own chain are left out and counted like one_case's."""
+    from vr180_convert_amd import chromatic, remapper
+
+    CHROMA["drawn"] += 1
+    spec, rot_at = rand_spec(rng)
+    h, w = rand_size(rng, 0.0, 2), rand_size(rng, 0.0, 2)
+    wo, ho = rand_size(rng, 0.0), rand_size(rng, 0.0)
+    interp = int(rng.choice([0, 1, 1, 2, 3, 4]))
+    border = int(rng.integers(0, 6))
+    bval = tuple(int(v) for v in rng.integers(0, 256, 3))
+    radius = float(rng.uniform(0.25, 0.7) * min(h, w)) * (-1 if rng.random() < 0.05 else 1)
+    n = int(rng.choice([1, 1, 2, 3]))
+
+    def coefs():
+        if rng.random() < 0.15:
+            return None
+        c = [0.0, 1.0 + float(rng.uniform(-0.02, 0.02)), 0.0, float(rng.uniform(-0.02, 0.02))]
+        if rng.random() < 0.15:
+            c[0] = float(rng.normal(0, 0.01))
+        return c[:2] if rng.random() < 0.2 else c
+
+    co = {"b": coefs(), "g": coefs() if rng.random() < 0.2 else None, "r": coefs()}
+    ca = chromatic.ChromaticAberration(red=co["r"], blue=co["b"], green=co["g"])
+    rots = None
+    if rot_at is not None and n > 1 and rng.random() < 0.4:
+        rots = [rand_rot(rng, rng.random() < 0.3) for _ in range(n)]
+    imgs = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for _ in range(n)]
+    fills = [rng.integers(0, 256, (ho, wo, 3), dtype=np.uint8) for _ in range(n)]
+    srcs = [make_view(rng, im, dev, True) for im in imgs]
+    dsts = [make_view(rng, f, dev, True) for f in fills]
+    paths = V.remap_tensors(CS.to_product(spec), srcs, dsts, radius=radius, interpolation=interp, boarder_mode=border, boarder_value=bval,
+                            chromatic=ca, **({} if rots is None else {"rotations": rots}))
+    kinds = remapper.last_launch_kinds()
+    for kd in kinds:
+        KINDS[kd] = KINDS.get(kd, 0) + 1
+    CHROMA["fixup"] += any(kd.endswith("+fixup") for kd in kinds)
+    CHROMA["literal"] += "literal" in paths
+    bad = 0
+    for k in range(n):
+        spec_k = spec if rots is None else spec[:rot_at] + [("rot", rots[k].tolist())] + spec[rot_at + 1:]
+        got = dsts[k].cpu().numpy()
+        for c, name in enumerate("bgr"):
+            spec_c = spec_k + [("poly", list(ca.coefs(name)))] if ca.coefs(name) is not None else spec_k
+            xm, ym = O.get_map(spec_c, radius=radius, size_input=(h, w), size_output=(wo, ho))
+            want = O.remap(imgs[k], xm, ym, interp, border, bval, dst=fills[k].copy())[..., c]
+            d = got[..., c] != want
+            if d.any():
+                ill = ill_conditioned(spec_c, radius, (h, w), (wo, ho))
+                if border in (1, 2, 3, 4):  # (one_case's rule for the modes that read the source far outside; NaN counts as singular)
+                    ill |= ~((np.abs(xm) < 2.0 ** 20) & (np.abs(ym) < 2.0 ** 20))
+                SINGULAR[0] += int((d & ill).sum())
+                d &= ~ill
+            if d.any():
+                tie = float32_ties(spec_c, radius, (h, w), (wo, ho))
+                TIES[0] += int((d & tie).sum())
+                d &= ~tie
+            if d.any() and DUMP[0]:
+                jj, ii = np.argwhere(d)[0]
+                print(f"  unit {k} channel {name}: {int(d.sum())} bytes differ, first (row {jj}, col {ii}) map=({xm[jj, ii]!r}, {ym[jj, ii]!r}) "
+                      f"got={int(got[jj, ii, c])} want={int(want[jj, ii])}")
+            bad += int(d.sum())
+    return (f"chroma spec={spec} {co} {h}x{w} -> {wo}x{ho} x{n} interp {interp} border {border} bval {bval} radius {radius!r} "
+            f"rots={'per unit' if rots is not None else 'no'} paths {paths} kinds {kinds}"), bad
 
 
 def feat_draw(rng) -> dict:
@@ -1710,6 +1780,7 @@ def main() -> int:
     ap.add_argument("--jpegodd", type=float, default=0.0, help="share of cases through the device JPEG decoders with a legal file of unusual structure or one damaged header, against tests/jpgodd_cases.py")
     ap.add_argument("--circle", type=float, default=0.0, help="share of cases through the image-circle fit (v1c_fit_circle) against circle_ref.fit, a part of them remaps with random off-centre center= against the oracle")
     ap.add_argument("--colormatch", type=float, default=0.0, help="share of cases through the colour match of two eyes (color_match_luts_tensor, apply_luts_tensor) against colormatch_ref, byte for byte")
+    ap.add_argument("--chroma", type=float, default=0.0, help="share of the remap (chain) cases that draw a ChromaticAberration (remap_tensors(chromatic=)) and are held to the per-channel oracle composition")
     ap.add_argument("--cases", type=int, default=None, help="stop after this many cases (before --seconds runs out)")
     ap.add_argument("--feat", type=float, default=0.0, help="share of cases through the feature pipeline (features.detect / features.match) against tests/feat_ref.py")
     ap.add_argument("--only", type=int, default=None, help="run only this case number (reproduce)")
@@ -1793,6 +1864,8 @@ def main() -> int:
                 desc, bad = auto_case(rng, dev)
             elif r_kind < a.lut + 0.05 + a.api + a.auto + a.fused:
                 desc, bad = fused_case(rng, dev)
+            elif a.chroma > 0 and rng.random() < a.chroma:  # (no draw when the option is off: earlier seeds replay as they ran)
+                desc, bad = chroma_case(rng, dev)
             else:
                 desc, bad = one_case(rng, dev, a.big)
         except Exception as e:  # noqa: BLE001 -- a refusal of the product (documented limits) is reported, not fatal
@@ -1824,7 +1897,8 @@ def main() -> int:
         + (f"; jpegodd cases: {ODD['drawn']} drawn, {ODD['legal']} legal files and {ODD['damage']} damaged headers, {ODD['refused']} of them refused as predicted"
            if ODD["drawn"] else "")
         + (f"; circle cases: {CIRCLE['drawn']} drawn" if CIRCLE["drawn"] else "")
-        + (f"; colormatch cases: {COLORMATCH['drawn']} drawn" if COLORMATCH["drawn"] else ""))
+        + (f"; colormatch cases: {COLORMATCH['drawn']} drawn" if COLORMATCH["drawn"] else "")
+        + (f"; chroma cases: {CHROMA['drawn']} drawn, {CHROMA['fixup']} with a fix-up pass, {CHROMA['literal']} on the literal path" if CHROMA["drawn"] else ""))
     say("kernel families of the chain cases' launch groups: " + ", ".join(f"{k} x{v}" for k, v in sorted(KINDS.items())))
     return 1 if n_bad else 0
 

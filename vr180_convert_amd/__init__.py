@@ -38,6 +38,10 @@ def __getattr__(name: str):
         from . import colormatch
 
         return getattr(colormatch, name)
+    if name == "ChromaticAberration":  # (likewise: a remap without chromatic= imports none of chromatic.py)
+        from . import chromatic
+
+        return chromatic.ChromaticAberration
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -105,4 +109,6 @@ __all__ = [
     "match_eyes_tensors",
     "color_match_report",
     "ColorMatchReport",
+    # lateral chromatic aberration corrected inside the remap, one map per colour channel (chromatic= / --chromatic)
+    "ChromaticAberration",
 ]

@@ -16,8 +16,9 @@ BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_1
 # v1c_plan_last_launch (tests / bench): which kernels served the last launch group; | LAUNCH_FIXUP when a fix-up pass followed
 LAUNCH_GENERIC, LAUNCH_TILE, LAUNCH_MIRROR, LAUNCH_CN, LAUNCH_CN_ROT, LAUNCH_BATCH, LAUNCH_ROT_PAIR, LAUNCH_FIXUP = 0, 1, 2, 3, 4, 5, 6, 0x100
 LAUNCH_WIDE = 7
+LAUNCH_CHROMA = 8  # v1c_ca_plan_last_launch (chromatic.py)
 LAUNCH_NAMES = {LAUNCH_GENERIC: "generic", LAUNCH_TILE: "tile", LAUNCH_MIRROR: "mirror", LAUNCH_CN: "cn", LAUNCH_CN_ROT: "cn_rot",
-                LAUNCH_BATCH: "batch", LAUNCH_ROT_PAIR: "rot_pair", LAUNCH_WIDE: "wide"}
+                LAUNCH_BATCH: "batch", LAUNCH_ROT_PAIR: "rot_pair", LAUNCH_WIDE: "wide", LAUNCH_CHROMA: "chroma"}
 # pixel types (cv2 depth codes): v1c_plan_create_ex / v1c_remap_lut_ex
 DEPTH_8U, DEPTH_16U, DEPTH_32F = 0, 2, 5
 

@@ -92,6 +92,25 @@ def parse_center(center: str, *, pair: bool = True, swap: bool = False) -> Any:
     return (pts[1], pts[0]) if swap else (pts[0], pts[1])
 
 
+def parse_chromatic(text: str, *, pair: bool = True, swap: bool = False) -> Any:
+    """``--chromatic``: '' -> None, 'r:c0,c1,...;b:c0,c1,...' -> a ChromaticAberration (channels r, g, b; each a PolynomialScaler's
+    coefs_reverse, 1.0 = the rim of the image circle), and for a pair of eyes 'LEFT|RIGHT' -> one per eye, which ``swap`` exchanges with
+    the eyes"""
+    if text == "":
+        return None
+    from . import chromatic
+
+    try:
+        if not pair and "|" in text:
+            raise ValueError("one image per map: no per-eye 'LEFT|RIGHT' form here")
+        ca = chromatic.parse_pair(text) if pair else chromatic.parse(text)
+    except ValueError as e:
+        raise typer.BadParameter(f"--chromatic {text}: {e}") from e
+    if isinstance(ca, tuple) and swap:
+        return (ca[1], ca[0])
+    return ca
+
+
 def closest_in_time(directory: Path, anchor: Path, offset_s: float) -> Path:
     """The file under ``directory`` (recursively) with ``anchor``'s suffix whose modification time is closest to
     ``anchor``'s, shifted by ``offset_s`` seconds (cli.py:178-216)."""
@@ -258,9 +277,15 @@ def lr(
                                                                       "distributions); 8-bit images; default: off")] = "",
     match_reference: Annotated[str, typer.Option("--match-reference", help="With --match-colors: the eye of the result that stays as it "
                                                                             "is, 'left' or 'right' (after --swap)")] = "left",
+    chromatic: Annotated[str, typer.Option("--chromatic", help="Correct lateral chromatic aberration inside the remap: "
+                                                                "'r:c0,c1,...;b:c0,c1,...' -- per channel a polynomial in the normalised "
+                                                                "source radius (1.0 = the rim), lowest order first; 'LEFT|RIGHT' for one "
+                                                                "per eye (swapped by --swap); 8-bit BGR images; default: off")] = "",
 ) -> None:
     """Remap a pair of fisheye images to a pair of SBS equirectangular images."""
     from .remapper import apply_lr
+
+    chromatic_ = parse_chromatic(chromatic, swap=swap)
 
     if match_colors not in ("", "gain", "histogram"):
         raise typer.BadParameter(f"--match-colors {match_colors}: expected 'gain' or 'histogram'")
@@ -309,7 +334,8 @@ def lr(
              **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}),
              **({"device_jpeg_optimize": True} if device_jpeg_optimize else {}),
              **({"device_decode_progressive": True} if device_decode_progressive else {}),
-             **({"match_colors": match_colors, "match_reference": match_reference} if match_colors else {}))
+             **({"match_colors": match_colors, "match_reference": match_reference} if match_colors else {}),
+             **({} if chromatic_ is None else {"chromatic": chromatic_}))
 
 
 @app.command()
@@ -340,9 +366,15 @@ def s(
     device_decode_progressive: Annotated[bool, typer.Option("--device-decode-progressive", help="With --device-decode or --device-decode-batch: "
                                                                                                  "progressive JPEG inputs are decoded on "
                                                                                                  "the GPU too")] = False,
+    chromatic: Annotated[str, typer.Option("--chromatic", help="Correct lateral chromatic aberration inside the remap: "
+                                                                "'r:c0,c1,...;b:c0,c1,...' -- per channel a polynomial in the normalised "
+                                                                "source radius (1.0 = the rim), lowest order first; 8-bit BGR images; "
+                                                                "default: off")] = "",
 ) -> None:
     """Remap fisheye images to equirectangular images (one shared map for all of them)."""
     from .remapper import apply
+
+    chromatic_ = parse_chromatic(chromatic, pair=False)
 
     if out_path == Path(""):
         out_paths = [p.with_suffix(f".out.{DEFAULT_EXTENSION}") for p in in_paths]
@@ -359,7 +391,8 @@ def s(
           **({"device_png": True} if device_png else {}), **({"device_jpeg": "batch"} if device_jpeg_batch else {"device_jpeg": True} if device_jpeg else {}),
           **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}),
           **({"device_jpeg_optimize": True} if device_jpeg_optimize else {}),
-          **({"device_decode_progressive": True} if device_decode_progressive else {}))
+          **({"device_decode_progressive": True} if device_decode_progressive else {}),
+          **({} if chromatic_ is None else {"chromatic": chromatic_}))
 
 
 @app.command()

@@ -441,6 +441,14 @@ static RadialTable cached_radial_table(const TableSpec& sp)
             }).table;
 }
 
+// the same cache for the plans of chroma.hip
+namespace v1c {
+RadialTable cached_radial_table_for(const TableSpec& sp)
+{
+    return cached_radial_table(sp);
+}
+}  // namespace v1c
+
 // (the key of the table the polynomials belong to: the spec it was fitted from, variable chosen)
 static MPolyTable cached_mpoly_table(const std::vector<v1c_op>& radial, const RadialTable& table)
 {

@@ -292,6 +292,11 @@ def clear_caches() -> None:
         _LOWERED.clear()
         _LAST_SHARED[0] = None
         _AUTO_LAST.clear()
+    import sys
+
+    ca = sys.modules.get(__package__ + ".chromatic")  # (its plans too, when the module was ever used)
+    if ca is not None:
+        ca.clear_caches()
 
 
 def _plan_for(chain: _abi.Chain, *, src_hw, dst_wh, cn, interpolation, border_mode, border_value, device,
@@ -443,6 +448,7 @@ def remap_tensors(
     size_input: tuple[int, int] | None = None,
     rotations: Sequence[Any] | None = None,
     center: Any = None,
+    chromatic: Any = None,
 ) -> list[str]:
     """Device-resident core of ``apply``: remap every ``srcs[k]`` into ``dsts[k]`` (same device,
     same shapes) on the current stream.  ``transformer`` is one chain shared by all units
@@ -452,14 +458,27 @@ def remap_tensors(
     ``center``: the image circle's centre in source pixels instead of ``(W_in // 2, H_in // 2)`` -- one ``(cx, cy)`` for every unit,
     one per unit (``None`` entries keep the frame's), or ``"auto"``: fitted from every source (``circle.fit_circle``, rounded to
     1/4 px; units whose centres agree still share a launch).
+    ``chromatic``: a ``chromatic.ChromaticAberration`` (or one per unit) -- lateral chromatic aberration corrected inside the remap, one
+    map per colour channel: channel ``c`` of every result is channel ``c`` of what this call gives for ``transformer *
+    PolynomialScaler(coefs_c)``.  uint8 BGR images and lowerable chains only: ValueError (not 3-channel), TypeError (uint16 / float32),
+    NotImplementedError (a chain that cannot be lowered), before anything is launched.  ``None``: nothing of it runs.
     Returns the code path used per launch group ('ray' / 'literal' / 'lut').  Nothing is
     synchronised (``center="auto"`` synchronises once per source)."""
     n = len(srcs)
     if n == 0:
         return []
+    if chromatic is not None:
+        from . import chromatic as _ca
+
+        _ca.check_images(list(srcs) + list(dsts))
     centers = None
     if center is not None:
         centers = per_unit_centers(fit_centers(center, srcs) if isinstance(center, str) else center, n)
+    if chromatic is not None:
+        paths, _TLS.plans = _ca.remap_tensors_chromatic(transformer, srcs, dsts, chromatic, radius=radius, interpolation=interpolation,
+                                                        boarder_mode=boarder_mode, boarder_value=boarder_value, size_input=size_input,
+                                                        rotations=rotations, centers=centers)
+        return paths
     if rotations is not None:
         return _remap_with_rotations(transformer, srcs, dsts, rotations, radius=radius, interpolation=interpolation,
                                      boarder_mode=boarder_mode, boarder_value=boarder_value, size_input=size_input, centers=centers)
@@ -635,11 +654,21 @@ def get_map(
     size_output: tuple[int, int] = (2048, 2048),
     device: Any = None,
     center: Any = None,
+    chromatic: Any = None,
+    channel: str | None = None,
 ) -> tuple[NDArray[np.float32], NDArray[np.float32]]:
     """Generate the remap map (reference remapper.py:23-59): float32 ``xmap, ymap`` of shape
     ``(size_output[1], size_output[0])``.  Evaluated on the GPU by the same code the fused kernel
     uses; non-lowerable chains are evaluated through their own ``transform`` like the reference.
-    ``center`` = (cx, cy): the image circle's centre instead of ``(W_in // 2, H_in // 2)`` (``"auto"`` needs an image: ValueError)."""
+    ``center`` = (cx, cy): the image circle's centre instead of ``(W_in // 2, H_in // 2)`` (``"auto"`` needs an image: ValueError).
+    ``chromatic`` with ``channel`` = "b" / "g" / "r": that channel's map under a ``chromatic.ChromaticAberration``."""
+    if chromatic is not None or channel is not None:
+        from . import chromatic as _ca
+
+        if chromatic is None or channel is None:
+            raise ValueError('get_map: chromatic= and channel= ("b", "g" or "r") go together')
+        return _ca.get_map_channel(transformer, chromatic, channel, radius=radius, size_input=size_input, size_output=size_output,
+                                   device=device, center=center)
     try:
         chain = lower_for_get_map(transformer, radius=radius, size_input=size_input, size_output=size_output, center=center)
     except NotLowerable:
@@ -790,6 +819,7 @@ def apply(
     device_jpeg_optimize: bool = False,
     device_decode_progressive: bool = False,
     center: Any = None,
+    chromatic: Any = None,
 ) -> Sequence[NDArray[np.uint8]]:
     """Apply transformer to images (reference remapper.py:324-403).
 
@@ -814,7 +844,10 @@ def apply(
 
     ``center``: the image circle's centre in source pixels instead of ``(W_in // 2, H_in // 2)`` -- ``(cx, cy)`` for all images, one
     per image, or ``"auto"``: every image's own, fitted on the device (circle.py) and rounded to 1/4 px.  ``radius="fit"``: the fitted
-    radius (``get_radius_smart``); the radius stays shared, the maximum over the images, whatever the centres."""
+    radius (``get_radius_smart``); the radius stays shared, the maximum over the images, whatever the centres.
+
+    ``chromatic``: a ``chromatic.ChromaticAberration`` -- lateral chromatic aberration corrected inside the remap, one map per colour
+    channel (``remap_tensors``); uint8 BGR images and lowerable chains only, refused before anything is launched."""
     device_jpeg = _device_jpeg_mode(device_jpeg)
     jpeg_kw = {"optimize": True} if device_jpeg_optimize else {}
     in_paths_ = [in_paths] if isinstance(in_paths, (str, Path, np.ndarray, torch.Tensor)) else in_paths
@@ -828,6 +861,14 @@ def apply(
         decoded = next((im for im in images if isinstance(im, torch.Tensor) and im.is_cuda), None)
         if decoded is not None:
             images = [_to_device(im, decoded.device) for im in images]
+    ca_kw: dict = {}
+    if chromatic is not None:
+        from . import chromatic as _ca
+
+        if not isinstance(chromatic, _ca.ChromaticAberration):  # (one map serves every image: one correction)
+            raise TypeError(f"apply: chromatic must be one ChromaticAberration, not {chromatic!r}")
+        _ca.check_images(images)
+        ca_kw = {"chromatic": chromatic}
     fits = None
     if (isinstance(radius, str) and radius == "fit") or isinstance(center, str):
         if isinstance(center, str) and _capturing():
@@ -852,7 +893,7 @@ def apply(
 
         def _group(srcs_g, dsts_g):
             remap_tensors(transformer, srcs_g, dsts_g, radius=radius_, interpolation=interpolation, boarder_mode=boarder_mode,
-                          boarder_value=boarder_value, size_input=size_in, center=center_)
+                          boarder_value=boarder_value, size_input=size_in, center=center_, **ca_kw)
 
         results = _hostpipe.run(imgs3, dev, (size_output[1], size_output[0], int(imgs3[0].shape[2])), _group)
         results = [r[..., 0] if a.ndim == 2 else r for r, a in zip(results, host_imgs)]
@@ -867,7 +908,7 @@ def apply(
         for d in dsts:  # cv2 leaves skipped pixels uninitialised; make them deterministic
             d.zero_()
     remap_tensors(transformer, srcs, dsts, radius=radius_, interpolation=interpolation, boarder_mode=boarder_mode,
-                  boarder_value=boarder_value, size_input=(int(srcs[0].shape[0]), int(srcs[0].shape[1])), center=center_)
+                  boarder_value=boarder_value, size_input=(int(srcs[0].shape[0]), int(srcs[0].shape[1])), center=center_, **ca_kw)
     if on_device:
         results: list[Any] = dsts
     else:
@@ -1017,6 +1058,7 @@ def apply_lr_tensors(
     center: Any = None,
     match_colors: Literal["gain", "histogram"] | None = None,
     match_reference: Literal["left", "right"] = "left",
+    chromatic: Any = None,
 ) -> torch.Tensor:
     """Device-resident ``apply_lr`` (merge=False): both eyes are remapped by ONE launch straight
     into the halves of the ``(H, 2W, C)`` side-by-side tensor (remapper.py:460-484, 517-518).
@@ -1040,12 +1082,27 @@ def apply_lr_tensors(
 
     ``match_colors``: ``"gain"`` or ``"histogram"`` -- after the remap, the half that is not ``match_reference`` is rewritten in place so
     that its colours match the other half's (colormatch.py; three more launches on the current stream, nothing synchronised, so it goes
-    into a graph capture with the remap).  uint8 eyes only: ValueError before anything is remapped.  None: nothing of it runs."""
+    into a graph capture with the remap).  uint8 eyes only: ValueError before anything is remapped.  None: nothing of it runs.
+
+    ``chromatic``: a ``chromatic.ChromaticAberration`` for both eyes -- one launch of two units -- or ``(left, right)``, one per eye: two
+    plans.  Lateral chromatic aberration corrected inside the remap, one map per colour channel (``remap_tensors``).  uint8 BGR eyes and
+    lowerable chains only; ``radius="auto"`` takes its exact form (``auto_radius_on_device=True``: NotImplementedError).  All refused
+    before anything is launched.  None: nothing of it runs."""
+    ca_kw: dict = {}
+    if chromatic is not None:
+        from . import chromatic as _ca
+
+        _ca.as_per_unit(chromatic, 2)
+        _ca.check_images([left, right])
+        if auto_radius_on_device:
+            raise NotImplementedError("chromatic: the device-resident radius=\"auto\" form is not served; pass auto_radius_on_device=None "
+                                      "(the exact form) or a numeric radius")
+        ca_kw = {"chromatic": chromatic}
     if match_colors is not None:
         _check_match_colors(match_colors, match_reference, left, right)
         out = apply_lr_tensors(transformer, left, right, out=out, size_output=size_output, interpolation=interpolation,
                                boarder_mode=boarder_mode, boarder_value=boarder_value, radius=radius,
-                               auto_radius_on_device=auto_radius_on_device, center=center)
+                               auto_radius_on_device=auto_radius_on_device, center=center, **ca_kw)
         from . import colormatch
 
         colormatch.match_eyes_tensors(out[:, : size_output[0]], out[:, size_output[0]:], mode=match_colors, reference=match_reference)
@@ -1071,7 +1128,7 @@ def apply_lr_tensors(
         on_dev = auto_radius_on_device
         if on_dev is None:
             on_dev = bool(torch.cuda.is_current_stream_capturing())
-        if on_dev:
+        if on_dev and not ca_kw:
             try:
                 if isinstance(transformer, tuple):  # per-eye transformer AND per-eye radius (remapper.py:460-473)
                     for k, (t, im, d) in enumerate(zip(transformer, (left, right), halves)):
@@ -1101,17 +1158,18 @@ def apply_lr_tensors(
              for im, f in zip((left, right), fits or (None, None))]
         if r[0] == r[1]:
             remap_tensors(list(transformer), [left, right], halves, radius=r[0], interpolation=interpolation,
-                          boarder_mode=boarder_mode, boarder_value=boarder_value, center=centers)
+                          boarder_mode=boarder_mode, boarder_value=boarder_value, center=centers, **ca_kw)
         else:
             for k, (t, im, d, rr) in enumerate(zip(transformer, (left, right), halves, r)):
+                ca_k = {"chromatic": _ca.as_per_unit(chromatic, 2)[k]} if ca_kw else {}
                 remap_tensors(t, [im], [d], radius=rr, interpolation=interpolation, boarder_mode=boarder_mode,
-                              boarder_value=boarder_value, center=None if centers is None else centers[k])
+                              boarder_value=boarder_value, center=None if centers is None else centers[k], **ca_k)
     else:
         r_ = get_radius_smart(radius, [left, right]) if fits is None else get_radius_smart(radius, [left, right], fits=fits)
         size_in = (int(left.shape[0]), int(left.shape[1]))
-        if centers is not None:  # (the launch that reads a moved radius from device memory is keyed without a centre: the planned path)
+        if centers is not None or ca_kw:  # (the launch that reads a moved radius from device memory is keyed without a centre: the planned path)
             remap_tensors(transformer, [left, right], halves, radius=r_, interpolation=interpolation,
-                          boarder_mode=boarder_mode, boarder_value=boarder_value, size_input=size_in, center=centers)
+                          boarder_mode=boarder_mode, boarder_value=boarder_value, size_input=size_in, center=centers, **ca_kw)
         elif not (isinstance(radius, str) and radius == "auto" and
                 _remap_host_radius(transformer, [left, right], halves, float(r_), interpolation=interpolation, boarder_mode=boarder_mode,
                                    boarder_value=boarder_value, size_input=size_in)):
@@ -1170,6 +1228,7 @@ def apply_lr(
     center: Any = None,
     match_colors: Literal["gain", "histogram"] | None = None,
     match_reference: Literal["left", "right"] = "left",
+    chromatic: Any = None,
 ) -> None:
     """Apply transformer to a pair of images and save them side by side (reference
     remapper.py:406-520).  ``left_path == right_path`` means one file holding both eyes.
@@ -1194,7 +1253,9 @@ def apply_lr(
     ``match_colors``, ``match_reference``: as in ``apply_lr_tensors`` -- the colours of one remapped eye matched to the other's on the
     device, before the anaglyph of ``merge=True`` and before every writer.  ValueError for a pair that is not uint8, before anything is
     remapped.  Where the result comes to the host anyway, a match that ended in a status (too few pixels in the mask) is logged as a
-    warning; the device writers leave the report on the device."""
+    warning; the device writers leave the report on the device.
+    ``chromatic``: as in ``apply_lr_tensors`` -- a ``chromatic.ChromaticAberration`` or ``(left, right)``; the remap's result is what
+    ``match_colors``, ``merge`` and every writer then see."""
     vr180 = isinstance(device_jpeg, str) and device_jpeg == "vr180"
     device_jpeg = True if vr180 else _device_jpeg_mode(device_jpeg)
     if vr180 and merge:
@@ -1214,6 +1275,13 @@ def apply_lr(
         left_path = image[:, : image.shape[1] // 2]
         right_path = image[:, image.shape[1] // 2 :]
     left, right = _io.imread_many([left_path, right_path])  # (two files: decoded side by side, the codecs release the GIL)
+    ca_kw: dict = {}
+    if chromatic is not None:  # (refused before the device is looked at)
+        from . import chromatic as _ca
+
+        _ca.as_per_unit(chromatic, 2)
+        _ca.check_images([left, right])
+        ca_kw = {"chromatic": chromatic}
     on_device = isinstance(left, torch.Tensor) and left.is_cuda
     dev = left.device if on_device else _device(device)
     if match_colors is not None:
@@ -1222,7 +1290,7 @@ def apply_lr(
     # "auto" radius: estimated on the host images when they are numpy (one row each)
     sbs = apply_lr_tensors(transformer, lt, rt, size_output=size_output, interpolation=interpolation,
                            boarder_mode=boarder_mode, boarder_value=boarder_value,
-                           radius=_radius_for_pair(radius, transformer, left, right), center=center)
+                           radius=_radius_for_pair(radius, transformer, left, right), center=center, **ca_kw)
     match_report = _match_sbs_colors(sbs, size_output[0], match_colors, match_reference) if match_colors is not None else None
     if merge and sbs.dtype != torch.uint8:
         # 16-bit / float32: the reference's own NumPy expression (remapper.py:485-497) on the host copy (the anaglyph kernel is 8-bit)
