@@ -439,6 +439,161 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(REST ? V1C_
 }
 #endif
 
+// ---- the seq kernel on a plan's tap table (tap_table.hpp) ----
+// The lane's map evaluation -- row / column loads, the radial-table slice and its barrier phase, the fp64 coordinates -- depends on the
+// plan only; for plans without rest tiles plan.hip has it done once (k_fill_tap_table below) and keeps 12 bytes per lane.  This kernel is
+// mirror_seq_tile<., REST = 0, REC = 1> with that block replaced: the wave's first request brings its own 64 entries (768 bytes) into a
+// 3 KB area that takes the place of the table slice, the first counted wait publishes them as it published the slice, and each lane
+// decodes its entry into the same 8 tap addresses and 8 weight pairs.  One instantiation: VAR_W and the polynomial's variable are the
+// fill's business.  Requests, stores and waits behind the decode are the computing kernel's, statement by statement.
+// (The 768 bytes travel as 48 lanes of the 16-byte form: lane-linear in LDS, which the 12-byte form is not -- tools/ubench/dma_raw_forms.hip.)
+constexpr int kTapSliceBytes = 256 * kTapEntryBytes;
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V1C_SEQ_WAVES + 1, 8))) void k_ray_lin3_pair_mirror_seq_tab(V1C_MIRROR_HEAD, TileArgs a_)
+{
+    constexpr int NT = 256;
+    __shared__ __attribute__((aligned(16))) uint32_t tapw[kTapSliceBytes / 4];
+    extern __shared__ __attribute__((aligned(16))) uint32_t dyn_box[];  // 2 raw boxes of a.kb KB
+    if (V1C_PRIO & 4)
+        __builtin_amdgcn_s_setprio(3);
+    args_cref a = kernel_args<kMirrorHeadBytes>();
+    const int tid = threadIdx.x;
+    const unsigned tiles_x = gx_rest & 0xffffu;
+    int tx, ty;
+    {
+        const unsigned slen = ((rows_strip >> 16) * tiles_x) & 0x7fffffffu;
+        xcd_tile_at(tiles_x_magic, slen, ((tiles_x_magic - 1u) >> 1) + 1u, tx, ty, rows_strip & 0xffffu, 0u, tiles_x, 0u);
+    }
+    const DstSize dsz{(int)(dst_wh & 0xffffu), (int)(dst_wh >> 16)};
+    const TileIds t = tile_ids(dsz, 0, tid, tx, ty, (int)tiles_x, NT / kLanesX);
+    const MirrorRec r = load_mirror_rec(pairs, t.box_tile);
+    const units_cptr U = (units_cptr)a.inl;
+    // the pair's pointers and pitches, read in one clause next to the record and held as values: left as loads, the compiler reads eye 1's
+    // source and both destinations again behind the barriers, where each is a round trip in front of a request or a store
+    const uint8_t* usrc[2] = {U[0].src, U[1].src};
+    uint8_t* udst[2] = {U[0].dst, U[1].dst};
+    uint32_t uspitch[2] = {(uint32_t)U[0].src_pitch, (uint32_t)U[1].src_pitch}, udpitch[2] = {(uint32_t)U[0].dst_pitch, (uint32_t)U[1].dst_pitch};
+    asm volatile("" : "+s"(usrc[0]), "+s"(usrc[1]), "+s"(udst[0]), "+s"(udst[1]), "+s"(uspitch[0]), "+s"(uspitch[1]), "+s"(udpitch[0]), "+s"(udpitch[1]));
+    const bool ualigned[2] = {((((uintptr_t)udst[0]) | (uintptr_t)udpitch[0]) & 3u) == 0, ((((uintptr_t)udst[1]) | (uintptr_t)udpitch[1]) & 3u) == 0};
+    const int cap_kb = (int)(kb_mh & 0xffffu);
+    if (!(r.flags & kMirrorRecFitSeq))
+        return;
+    const uint32_t lds_tap = (uint32_t)(uintptr_t)(lds_u32_ptr)(const uint32_t*)tapw;
+    const uint32_t raw_b = (uint32_t)(uintptr_t)(lds_u32_ptr)dyn_box, raw_q = raw_b + (uint32_t)cap_kb * 1024u;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    {  // this wave's 64 entries: the table is lane-linear within a tile pair (`rowcol_tables` of the head carries its base)
+        const uint32_t wave_off = (uint32_t)__builtin_amdgcn_readfirstlane(tid & ~63) * (uint32_t)kTapEntryBytes;
+        const uint8_t* gp = (const uint8_t*)rowcol_tables + ((size_t)(uint32_t)__builtin_amdgcn_readfirstlane(t.box_tile) * (size_t)kTapSliceBytes + wave_off) +
+                            (uint32_t)lane * 16u;
+        if (lane < 64 * kTapEntryBytes / 16)
+            __builtin_amdgcn_global_load_lds((glb_void_ptr)gp, (lds_void_ptr)(uintptr_t)(lds_tap + wave_off), 16, 0, 0);
+    }
+    const RawLanes mb = rec_lanes(r.b, lane), mq = rec_lanes(r.q, lane);
+    auto request = [&](int e, int which) {
+        const uint8_t* src = usrc[e];
+        const uint32_t sp = uspitch[e];
+        return which == 0 ? rec_box_dma(r.b, mb, src, sp, lane, wave, raw_b) : rec_box_dma(r.q, mq, src, sp, lane, wave, raw_q);
+    };
+    const int nb = request(0, 0);
+    const int nq = request(0, 1);
+    if (V1C_PRIO & 4)
+        __builtin_amdgcn_s_setprio(0);
+    wait_vm_barrier(nb + nq);  // the entries
+    const uint32_t pitch_b = r.b.lpitch, pitch_q = r.q.lpitch;
+    uint32_t ta_b[kPX], ta_q[kPX];
+    BlendW W_b[kPX], W_q[kPX];
+    {
+        const lds_u32_ptr ep = (lds_u32_ptr)(uintptr_t)(lds_tap + (uint32_t)tid * (uint32_t)kTapEntryBytes);
+        const TapCoords tc = tap_entry_decode(TapEntry{{ep[0], ep[1], ep[2]}});
+        const uint32_t kb = raw_b, kq = raw_q + (uint32_t)(r.b.x3 - r.q.x3);
+#pragma unroll
+        for (int k = 0; k < kPX; k++) {
+            const uint32_t ix = (uint32_t)tc.x[k] >> 5, x3 = ix * 2u + ix;
+            ta_b[k] = mad24_vsv((uint32_t)tc.y[k] >> 5, pitch_b, x3 + kb);
+            ta_q[k] = mad24_vsv((uint32_t)tc.y2[k] >> 5, pitch_q, x3 + kq);
+            W_b[k] = blend_weights(tc.x[k], tc.y[k]);
+            W_q[k] = blend_weights(tc.x[k], tc.y2[k]);
+        }
+    }
+    const uint32_t row_off = (uint32_t)t.x0 * 3u;
+    const int jm = (int)(kb_mh >> 16) - t.j;
+    const bool band_row = jm < dsz.dst_h;
+    auto drow = [&](int e, int j) { return mul24_vs((uint32_t)j, udpitch[e]) + row_off; };
+    uint32_t pix[kPX];
+    // ---- eye 0 ----
+    wait_vm_barrier(nq);  // tile box
+    gather_taps_raw(ta_b, W_b, pitch_b, pix);
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");  // band box landed; every wave has sampled the tile box
+    request(1, 0);
+    store4<1>(udst[0] + drow(0, t.j), pix, 0xFu, ualigned[0]);
+    gather_taps_raw(ta_q, W_q, pitch_q, pix);
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // every wave has sampled the band box
+    request(1, 1);
+    if (band_row)
+        store4<1>(udst[0] + drow(0, jm), pix, 0xFu, ualigned[0]);
+    // ---- eye 1 (behind its tile box: eye 0's tile store and its band's nq requests; the predicated band store is not counted) ----
+    wait_vm_barrier(nq + 1);
+    gather_taps_raw(ta_b, W_b, pitch_b, pix);
+    wait_vm_barrier_imm<0>();
+    store4<1>(udst[1] + drow(1, t.j), pix, 0xFu, ualigned[1]);
+    gather_taps_raw(ta_q, W_q, pitch_q, pix);
+    if (band_row)
+        store4<1>(udst[1] + drow(1, jm), pix, 0xFu, ualigned[1]);
+}
+
+// The fill: one workgroup per tile pair of tile rows 0 .. TY / 2, the lanes laid out as the mirror kernels lay them out (tile_ids), the
+// coordinates by the instantiation of lane_coords the seq kernel runs for this plan and tile (VAR_W; the tile's polynomial variable; the
+// tile's table slice, read where it lies), rebased on the box origins and packed.  A lane whose values do not fit an entry raises
+// `*overflow`: the plan then drops the table.
+template <int VAR_W>
+__global__ __launch_bounds__(256) void k_fill_tap_table(const KernelCtx* ctxp, const TileBox* __restrict__ boxes, const TileBox* __restrict__ mboxes,
+                                                        int tiles_x, uint32_t* __restrict__ table, uint32_t* overflow)
+{
+    ctx_cref c = *(const V1C_CONST KernelCtx*)ctxp;
+    ray_cref P = c.ray;
+    const int tid = threadIdx.x;
+    const TileIds t = tile_ids(c.g, 0, tid, (int)blockIdx.x, (int)blockIdx.y, tiles_x, 256 / kLanesX);
+    const TileBox b = boxes[t.box_tile], q = mboxes[t.box_tile];
+    RowCol rc;
+    load_rowcol<0>(P, t.xc, t.jc, rc);
+    const bool mpoly = (b.interior & 2) != 0;
+    const int nidx = max(b.nidx, 1), idx0 = max(b.idx0, 0);
+    const double* tab = (mpoly ? P.radial_m : P.radial) + (size_t)idx0 * kRadialCoefs;
+    LaneCoords L;
+    if (mpoly)
+        lane_coords<VAR_W, 0, 2, 0, 1, 1, 1, 0, 1>(c, nullptr, rc, kPX, tab, idx0, nidx, L);
+    else
+        lane_coords<VAR_W, 0, 2, 0, 1, 0, 1, 0, 1>(c, nullptr, rc, kPX, tab, idx0, nidx, L);
+    TapCoords tc;
+#pragma unroll
+    for (int k = 0; k < kPX; k++) {
+        tc.x[k] = (int)((uint32_t)L.sx[k] - kRoundBias) - 32 * b.x0;
+        tc.y[k] = (int)((uint32_t)L.sy[k] - kRoundBias) - 32 * b.y0;
+        tc.y2[k] = (int)((uint32_t)L.sy2[k] - kRoundBias) - 32 * q.y0;
+    }
+    if (!tap_entry_fits(tc))
+        atomicOr(overflow, 1u);
+    const TapEntry e = tap_entry_encode(tc);
+    uint32_t* out = table + ((size_t)t.box_tile * 256u + (size_t)tid) * 3u;
+    out[0] = e.w[0], out[1] = e.w[1], out[2] = e.w[2];
+}
+
+size_t tap_table_bytes(const Geom& g)
+{
+    const dim3 full = tile_grid(g, 256, 1);
+    return (size_t)full.x * (size_t)(full.y / 2 + 1) * (size_t)kTapSliceBytes;
+}
+
+hipError_t launch_fill_tap_table(const KernelCtx& c, const KernelCtx* cdev, const void* boxes, const void* mboxes, void* table, uint32_t* overflow)
+{
+    const dim3 full = tile_grid(c.g, 256, 1);
+    const dim3 grid(full.x, full.y / 2 + 1, 1), block(256, 1, 1);
+    if (c.ray.var_is_w)
+        hipLaunchKernelGGL((k_fill_tap_table<1>), grid, block, 0, 0, cdev, (const TileBox*)boxes, (const TileBox*)mboxes, (int)full.x, (uint32_t*)table, overflow);
+    else
+        hipLaunchKernelGGL((k_fill_tap_table<0>), grid, block, 0, 0, cdev, (const TileBox*)boxes, (const TileBox*)mboxes, (int)full.x, (uint32_t*)table, overflow);
+    return hipGetLastError();
+}
+
 // Rest list of the mirror launch; false when the plan cannot use it (geometry, or more remaining tiles than the
 // launch's first grid slice holds).
 // Box buffer size (wave-passes of 64 sixteen-byte units) of k_ray_lin3_pair_mirror_raw for a plan: the smallest that holds the
@@ -534,7 +689,7 @@ void tile_mirror_records(const void* host_boxes, const void* host_mboxes, size_t
 // seq_kb > 0 (pairs): k_ray_lin3_pair_mirror_seq, two box buffers of seq_kb KB, the eyes one after the other
 hipError_t launch_ray_lin3_pair_mirror(const KernelCtx& c, const KernelCtx* cdev, const LaunchUnits& lu, uint32_t* flags, const void* boxes,
                                        const void* mboxes, int half_dwords, int mirror_h, const uint32_t* rest_list, int n_rest, int raw_nwp,
-                                       hipStream_t stream, int seq_kb, const void* recs)
+                                       hipStream_t stream, int seq_kb, const void* recs, const void* tap_table)
 {
     const int n_eyes = lu.n;
     const dim3 full = tile_grid(c.g, 256, 1);
@@ -603,7 +758,18 @@ hipError_t launch_ray_lin3_pair_mirror(const KernelCtx& c, const KernelCtx* cdev
                     V1C_MIRROR_LAUNCH((k_ray_lin3_pair_mirror_seq_box<0, 0>), rgrid, slds, 0u);
                 return hipGetLastError();
             }
+            static const bool tab_off = [] {  // V1C_MIRROR_TAB=0 (A/B): the kernel that evaluates the map, whatever the plan holds
+                const char* e = tuning_env("V1C_MIRROR_TAB");
+                return e && e[0] == '0';
+            }();
+            if (tab_off)
+                tap_table = nullptr;
 #endif
+            if (tap_table) {  // the plan's tap table in the head's table slot: the kernel that reads its coordinates (one instantiation)
+                hipLaunchKernelGGL(k_ray_lin3_pair_mirror_seq_tab, rgrid, block, slds, stream, head_pairs, a.tiles_x_magic, full.x, rows_strip, dst_wh,
+                                   (const double*)tap_table, a.ctx, (unsigned)a.kb | (unsigned)a.mirror_h << 16, a);
+                return hipGetLastError();
+            }
             if (c.ray.var_is_w)
                 V1C_MIRROR_LAUNCH((k_ray_lin3_pair_mirror_seq<1, 0>), rgrid, slds, 0u);
             else

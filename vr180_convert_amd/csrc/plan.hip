@@ -204,6 +204,9 @@ static void border_for_depth(int depth, const double* bv, uint8_t cval8[4], floa
 // ------------------------------------------------------------------------------------------
 // plan
 // ------------------------------------------------------------------------------------------
+// no tap table (tap_table.hpp) above this size: a 4096 x 4096 pair plan holds 25.4 MB, a 16384 x 8192 one would hold 200
+static constexpr size_t kTapTableMaxBytes = (size_t)64 << 20;
+
 struct v1c_plan {
     int device = 0;
     int mode = MODE_LITERAL;
@@ -240,6 +243,11 @@ struct v1c_plan {
     // the mirror launch leaves to the pair kernel (k_ray_lin3_pair_mirror); mirror_boxes == nullptr: not used
     void* mirror_boxes = nullptr;
     const void* mirror_recs = nullptr;   // the same slots as launch records (tile_device.hpp: MirrorRec): what the seq / one-eye kernels read
+    // pairs without rest tiles: the lanes' tap coordinates, 12 bytes each (tap_table.hpp), filled at creation; nullptr: the plan has rest
+    // tiles, the table would pass kTapTableMaxBytes, some lane's values do not fit an entry, or there was no memory for it -- every
+    // launch then evaluates the map (one rule per plan: no launch mixes the two)
+    const void* tap_table = nullptr;
+    size_t tap_table_bytes = 0;
     const void* mirror_pairs = nullptr;  // tuning build: (tile box, band box) interleaved, 64 bytes per tile, for the kernels' A/B partners
     const uint32_t* mirror_rest = nullptr;
     int n_mirror_rest = 0;
@@ -834,6 +842,33 @@ extern "C" int v1c_plan_create_ex(v1c_plan** out, int device, const v1c_chain* c
                                 }
                                 p->mirror_recs = dr;
                             }
+                            // no rest tiles (C2: every tile pair fits the seq kernel's buffers): the lanes' coordinates, once per plan
+                            if (p->mirror_recs && p->mirror_seq_kb > 0 && mrest.empty() && tap_table_bytes(g) <= kTapTableMaxBytes) {
+                                const size_t tb = tap_table_bytes(g);
+                                void* tt = nullptr;
+                                uint32_t over = 1;
+                                if (hipMalloc(&tt, tb + 16) == hipSuccess) {  // (the overflow word behind the entries)
+                                    uint32_t* flag = (uint32_t*)((char*)tt + tb);
+                                    hipError_t te = hipMemset(flag, 0, 16);
+                                    if (te == hipSuccess)
+                                        te = launch_fill_tap_table(p->ctx, p->ctx_dev, p->tile_boxes, mbx, tt, flag);
+                                    if (te == hipSuccess)
+                                        te = hipMemcpy(&over, flag, sizeof(over), hipMemcpyDeviceToHost);
+                                    if (te != hipSuccess) {
+                                        (void)hipFree(tt);
+                                        v1c_plan_destroy(p);
+                                        return fail(V1C_E_HIP, std::string("tap table: ") + hipGetErrorString(te));
+                                    }
+                                    if (over == 0)
+                                        p->allocs.push_back(tt), p->tap_table = tt, p->tap_table_bytes = tb;
+                                    else
+                                        (void)hipFree(tt);
+                                } else {
+                                    (void)hipGetLastError();  // (no memory for the table: the plan works without it)
+                                }
+                                if (const char* dbg = tuning_env("V1C_DEBUG"); dbg && dbg[0] == '1')
+                                    std::fprintf(stderr, "[v1c] tap table: %zu bytes, %s\n", tb, p->tap_table ? "in use" : "not kept");
+                            }
                             std::vector<uint32_t> mrest1;
                             if (p->mirror_raw_nwp > 0 && tile_mirror_rest(hb.data(), hm.data(), g, p->half_dwords, g.dst_h, mrest1, p->mirror_raw_nwp, true, 1)) {
                                 if ((rc = upload(p, mrest1, &p->mirror_rest1))) {
@@ -894,6 +929,11 @@ extern "C" int v1c_debug_read_stamps(v1c_plan* p, unsigned long long* out8)
     return V1C_OK;
 }
 #endif
+
+extern "C" int64_t v1c_plan_tap_table_bytes(const v1c_plan* p)
+{
+    return p ? (int64_t)p->tap_table_bytes : 0;
+}
 
 extern "C" int v1c_plan_path(const v1c_plan* p)
 {
@@ -1171,7 +1211,7 @@ extern "C" int v1c_plan_run(v1c_plan* p, void* stream, const v1c_unit* units, in
             HIP_TRY(launch_ray_lin3_pair_mirror(p->ctx, p->ctx_dev, lu, flags, p->tile_boxes, p->mirror_raw_nwp > 0 ? p->mirror_pairs : p->mirror_boxes,
                                                 p->half_dwords, p->mirror_h,
                                                 n == 1 ? p->mirror_rest1 : p->mirror_rest, n == 1 ? p->n_mirror_rest1 : p->n_mirror_rest,
-                                                p->mirror_raw_nwp, st, p->mirror_seq_kb, p->mirror_recs));
+                                                p->mirror_raw_nwp, st, p->mirror_seq_kb, p->mirror_recs, n == 2 ? p->tap_table : nullptr));
         } else if (d.fast && p->ctx.g.cn != 3) {
             // grayscale / BGRA: k_ray_lin_cn (one table entry per lane; plan-time boxes for the plan's own rotation, boxes reduced in the
             // kernel -- one unit per workgroup, a 12 KB buffer -- for units that override it)

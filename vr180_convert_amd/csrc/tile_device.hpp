@@ -38,6 +38,7 @@
 #include <cstring>
 
 #include "kernels.hpp"
+#include "tap_table.hpp"
 
 // V1C_PRIO (bits): s_setprio 3 from a workgroup's first instruction until its box / table loads are requested (back to 0 behind them) --
 // 1: bicubic / Lanczos4 tile kernels, 2: bilinear tile kernels, 4: mirror kernels, 8: batch kernel.  A workgroup that has just started

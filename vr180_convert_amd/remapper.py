@@ -176,6 +176,12 @@ class Plan:
             return ""
         return _abi.LAUNCH_NAMES.get(k & 0xFF, "?") + ("+fixup" if k & _abi.LAUNCH_FIXUP else "")
 
+    def tap_table_bytes(self) -> int:
+        """Bytes of the plan's tap table (``v1c_plan_tap_table_bytes``): the per-lane tap coordinates a rest-free pair plan keeps so
+        that its launches need not evaluate the map; 0 when the plan holds none (or the library behind ``V1C_LIB`` predates it)."""
+        f = getattr(_native.lib(), "v1c_plan_tap_table_bytes", None)
+        return int(f(self._h)) if f is not None else 0
+
     def run(self, srcs: Sequence[torch.Tensor], dsts: Sequence[torch.Tensor], rots: Sequence[Any] | None = None) -> None:
         n = len(srcs)
         if n == 0 or len(dsts) != n or (rots is not None and len(rots) != n):
@@ -276,6 +282,12 @@ def last_launch_kinds() -> list[str]:
     'lut' per unit whose map came from the chain's own ``transform()``).  The engine serves the same bytes through several kernels; tests
     use this to make sure a case meant for a tiled kernel reached it."""
     return [p.last_launch() for p in getattr(_TLS, "plans", [])]
+
+
+def last_tap_table_bytes() -> list[int]:
+    """``Plan.tap_table_bytes`` per launch group of the calling thread's most recent ``remap_tensors`` / ``apply_lr_tensors`` call, in
+    the order of ``last_launch_kinds`` (0: that plan evaluates its map in every launch; units served from a host map count 0)."""
+    return [p.tap_table_bytes() if isinstance(p, Plan) else 0 for p in getattr(_TLS, "plans", [])]
 
 
 def last_auto_radius_form() -> str:
