@@ -253,11 +253,14 @@ enum {
 int v1c_plan_last_launch(const v1c_plan* plan);
 
 /* Bytes of the plan's tap table, 0 when it holds none.  Plans of BGR bilinear pairs of an unrotated chain whose every tile pair the
- * mirror kernel serves keep the fixed-point tap coordinates of every output pixel, 12 bytes per 4 pixels of the upper half of the
- * image, computed once at creation by the kernel's own coordinate code; their launches read them instead of evaluating the map.
+ * mirror kernel serves keep the fixed-point tap coordinates of every output pixel, per 4 pixels of the upper half of the image 12
+ * bytes, or 8 (the compact entry) where 12 would make a table of more than 8 MiB, computed once at creation by the kernel's own
+ * coordinate code; their launches read them instead of evaluating the map.  The size reported is the size allocated.
  * Plans whose table would pass 64 MB, or whose map does not fit the entry format somewhere, hold none and evaluate the map in every
  * launch: the same bytes either way.  For tests / bench and for callers that budget device memory.                              */
 int64_t v1c_plan_tap_table_bytes(const v1c_plan* plan);
+/* Bytes per entry of that table (12 or 8); 0 when the plan holds none. */
+int v1c_plan_tap_entry_bytes(const v1c_plan* plan);
 
 /* Evaluate only the coordinate chain on the output grid and store float32 maps (device
  * pointers, row pitch map_pitch bytes).  Replaces get_map(), remapper.py:23-59.  Used for

@@ -32,7 +32,7 @@ SYMBOLS = [
     "v1c_jpeg_compose_bound", "v1c_jpeg_compose_check", "v1c_jpeg_header_xf", "v1c_jpeg_compose",
     "v1c_fit_circle_workspace", "v1c_fit_circle_async", "v1c_fit_circle",
     "v1c_color_match_workspace", "v1c_color_match_luts_async", "v1c_apply_luts_async",
-    "v1c_plan_tap_table_bytes",
+    "v1c_plan_tap_table_bytes", "v1c_plan_tap_entry_bytes",
     "v1c_ca_plan_create", "v1c_ca_plan_run", "v1c_ca_plan_get_map", "v1c_ca_plan_path", "v1c_ca_plan_last_launch", "v1c_ca_plan_destroy",
 ]
 
@@ -171,6 +171,11 @@ def lib() -> C.CDLL:
     try:
         L.v1c_plan_tap_table_bytes.argtypes = [vp]
         L.v1c_plan_tap_table_bytes.restype = i64
+    except AttributeError:  # (an older build behind V1C_LIB)
+        pass
+    try:
+        L.v1c_plan_tap_entry_bytes.argtypes = [vp]
+        L.v1c_plan_tap_entry_bytes.restype = i32
     except AttributeError:  # (an older build behind V1C_LIB)
         pass
     L.v1c_plan_run.argtypes = [vp, vp, C.POINTER(_abi.Unit), i32]

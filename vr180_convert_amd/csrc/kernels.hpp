@@ -119,17 +119,23 @@ int tile_mirror_raw_passes(const void* host_boxes, const void* host_mboxes, cons
 // four-buffer / register-staged A/B partners
 hipError_t launch_ray_lin3_pair_mirror(const KernelCtx& c, const KernelCtx* cdev, const LaunchUnits& lu, uint32_t* flags, const void* boxes,
                                        const void* mboxes, int half_dwords, int mirror_h, const uint32_t* rest_list, int n_rest, int raw_nwp,
-                                       hipStream_t stream, int seq_kb, const void* recs = nullptr, const void* tap_table = nullptr);
-// The tap table of a pair plan without rest tiles (tap_table.hpp): 12 bytes per lane of every tile pair of tile rows 0 .. TY / 2, filled
-// once by the seq kernel's own coordinate code on the default stream; `*overflow` (a zeroed device word) is set when some lane's
-// values do not fit an entry -- the table is then not to be used.  `tap_table` of the launch: the filled table, or nullptr (every
-// launch evaluates the map: k_ray_lin3_pair_mirror_seq<., 0>); only read when n_rest == 0 and seq_kb > 0.
-size_t tap_table_bytes(const Geom& g);
-hipError_t launch_fill_tap_table(const KernelCtx& c, const KernelCtx* cdev, const void* boxes, const void* mboxes, void* table, uint32_t* overflow);
+                                       hipStream_t stream, int seq_kb, const void* recs = nullptr, const void* tap_table = nullptr,
+                                       int tap_entry_bytes = 12);
+// The tap table of a pair plan without rest tiles (tap_table.hpp): `entry_bytes` (12, or 8: the compact form) per lane of every tile pair
+// of tile rows 0 .. TY / 2, filled once by the seq kernel's own coordinate code on the default stream; `*overflow` (a zeroed device
+// word) is set when some lane's values do not fit an entry -- the table is then not to be used.  `tap_table` of the launch: the filled
+// table, or nullptr (every launch evaluates the map: k_ray_lin3_pair_mirror_seq<., 0>); only read when n_rest == 0 and seq_kb > 0.
+// tap_table_s: the plan's S of the compact form (the nearest integer to 64 x the source's row centre) -- what the fill and the records
+// (tile_mirror_records' `tap_s`) must agree on.
+size_t tap_table_bytes(const Geom& g, int entry_bytes = 12);
+int tap_table_s(const KernelCtx& c);
+hipError_t launch_fill_tap_table(const KernelCtx& c, const KernelCtx* cdev, const void* boxes, const void* mboxes, void* table, uint32_t* overflow,
+                                 int entry_bytes = 12);
 // The launch records of the seq and one-eye kernels (tile_device.hpp: MirrorRec), 64 bytes per tile in the order of the boxes: what a
 // tile pair's prologue derives from the plan alone, from the downloaded boxes.  `seq_kb` / `one_kb`: the two kernels' box buffers (0:
 // the plan does not launch that kernel).  `recs` of the launch: the uploaded records.
-void tile_mirror_records(const void* host_boxes, const void* host_mboxes, size_t n_tiles, const Geom& g, int seq_kb, int one_kb, std::vector<char>& out);
+void tile_mirror_records(const void* host_boxes, const void* host_mboxes, size_t n_tiles, const Geom& g, int seq_kb, int one_kb, std::vector<char>& out,
+                         int tap_s = 0);
 int tile_half_dwords(const void* host_boxes, size_t n_tiles, int max_chunks, bool occupancy_classes);
 // `coords_bounded` (launches without boxes): the host has bounded |32 x|, |32 y| < 2^21 for every pixel of every unit
 // (radial_table_g_bound): k_ray_lin3_rot_pair_raw evaluates its speculative coordinates without the clamps of the cvRound trick

@@ -9,6 +9,8 @@
 // (V1C_MIRROR_REC=0: k_ray_lin3_pair_mirror_seq_box, k_ray_lin3_pair_mirror_box_raw) keep the prologue that decodes the (tile box,
 // band box) pair, tests mirror_raw_fit and takes the reciprocals of the units per row in every wave.
 // Building blocks: tile_device.hpp.
+#include <cmath>
+
 #include "tile_device.hpp"
 
 namespace v1c {
@@ -447,12 +449,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(REST ? V1C_
 // decodes its entry into the same 8 tap addresses and 8 weight pairs.  One instantiation: VAR_W and the polynomial's variable are the
 // fill's business.  Requests, stores and waits behind the decode are the computing kernel's, statement by statement.
 // (The 768 bytes travel as 48 lanes of the 16-byte form: lane-linear in LDS, which the 12-byte form is not -- tools/ubench/dma_raw_forms.hip.)
-constexpr int kTapSliceBytes = 256 * kTapEntryBytes;
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V1C_SEQ_WAVES + 1, 8))) void k_ray_lin3_pair_mirror_seq_tab(V1C_MIRROR_HEAD, TileArgs a_)
+// EB = 8, the compact entry (TapEntry8): the same body; lanes 0 .. 31 of a wave issue the request (512 bytes), a lane reads its entry
+// with one 8-byte LDS read, the area is 2 KB, and the decode takes the tile pair's K from the record that came with the first scalar load.
+constexpr int kTapSliceBytes = 256 * kTapEntryBytes, kTap8SliceBytes = 256 * kTap8EntryBytes;
+template <int EB>
+__device__ __forceinline__ void mirror_seq_tab_tile(V1C_MIRROR_HEAD, uint32_t* tapw, uint32_t* dyn_box)
 {
+    static_assert(EB == kTapEntryBytes || EB == kTap8EntryBytes, "the 12-byte entry or the compact one");
     constexpr int NT = 256;
-    __shared__ __attribute__((aligned(16))) uint32_t tapw[kTapSliceBytes / 4];
-    extern __shared__ __attribute__((aligned(16))) uint32_t dyn_box[];  // 2 raw boxes of a.kb KB
     if (V1C_PRIO & 4)
         __builtin_amdgcn_s_setprio(3);
     args_cref a = kernel_args<kMirrorHeadBytes>();
@@ -481,10 +485,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V1C_SEQ_WAV
     const uint32_t raw_b = (uint32_t)(uintptr_t)(lds_u32_ptr)dyn_box, raw_q = raw_b + (uint32_t)cap_kb * 1024u;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     {  // this wave's 64 entries: the table is lane-linear within a tile pair (`rowcol_tables` of the head carries its base)
-        const uint32_t wave_off = (uint32_t)__builtin_amdgcn_readfirstlane(tid & ~63) * (uint32_t)kTapEntryBytes;
-        const uint8_t* gp = (const uint8_t*)rowcol_tables + ((size_t)(uint32_t)__builtin_amdgcn_readfirstlane(t.box_tile) * (size_t)kTapSliceBytes + wave_off) +
+        const uint32_t wave_off = (uint32_t)__builtin_amdgcn_readfirstlane(tid & ~63) * (uint32_t)EB;
+        const uint8_t* gp = (const uint8_t*)rowcol_tables + ((size_t)(uint32_t)__builtin_amdgcn_readfirstlane(t.box_tile) * (size_t)(256 * EB) + wave_off) +
                             (uint32_t)lane * 16u;
-        if (lane < 64 * kTapEntryBytes / 16)
+        if (lane < 64 * EB / 16)
             __builtin_amdgcn_global_load_lds((glb_void_ptr)gp, (lds_void_ptr)(uintptr_t)(lds_tap + wave_off), 16, 0, 0);
     }
     const RawLanes mb = rec_lanes(r.b, lane), mq = rec_lanes(r.q, lane);
@@ -502,8 +506,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V1C_SEQ_WAV
     uint32_t ta_b[kPX], ta_q[kPX];
     BlendW W_b[kPX], W_q[kPX];
     {
-        const lds_u32_ptr ep = (lds_u32_ptr)(uintptr_t)(lds_tap + (uint32_t)tid * (uint32_t)kTapEntryBytes);
-        const TapCoords tc = tap_entry_decode(TapEntry{{ep[0], ep[1], ep[2]}});
+        TapCoords tc;
+        if constexpr (EB == kTap8EntryBytes) {
+            typedef uint32_t __attribute__((ext_vector_type(2))) u32x2;
+            typedef const __attribute__((address_space(3))) u32x2* lds_u64_ptr;
+            const u32x2 ev = *(lds_u64_ptr)(uintptr_t)(lds_tap + (uint32_t)tid * (uint32_t)EB);
+            tc = tap8_decode(TapEntry8{{ev.x, ev.y}}, r.tap_k);
+        } else {
+            const lds_u32_ptr ep = (lds_u32_ptr)(uintptr_t)(lds_tap + (uint32_t)tid * (uint32_t)EB);
+            tc = tap_entry_decode(TapEntry{{ep[0], ep[1], ep[2]}});
+        }
         const uint32_t kb = raw_b, kq = raw_q + (uint32_t)(r.b.x3 - r.q.x3);
 #pragma unroll
         for (int k = 0; k < kPX; k++) {
@@ -540,13 +552,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V1C_SEQ_WAV
         store4<1>(udst[1] + drow(1, jm), pix, 0xFu, ualigned[1]);
 }
 
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V1C_SEQ_WAVES + 1, 8))) void k_ray_lin3_pair_mirror_seq_tab(V1C_MIRROR_HEAD, TileArgs a_)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t tapw[kTapSliceBytes / 4];
+    extern __shared__ __attribute__((aligned(16))) uint32_t dyn_box[];  // 2 raw boxes of a.kb KB
+    mirror_seq_tab_tile<kTapEntryBytes>(pairs, tiles_x_magic, gx_rest, rows_strip, dst_wh, rowcol_tables, ctxp, kb_mh, tapw, dyn_box);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V1C_SEQ_WAVES + 1, 8))) void k_ray_lin3_pair_mirror_seq_tab8(V1C_MIRROR_HEAD, TileArgs a_)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t tapw[kTap8SliceBytes / 4];
+    extern __shared__ __attribute__((aligned(16))) uint32_t dyn_box[];
+    mirror_seq_tab_tile<kTap8EntryBytes>(pairs, tiles_x_magic, gx_rest, rows_strip, dst_wh, rowcol_tables, ctxp, kb_mh, tapw, dyn_box);
+}
+
 // The fill: one workgroup per tile pair of tile rows 0 .. TY / 2, the lanes laid out as the mirror kernels lay them out (tile_ids), the
 // coordinates by the instantiation of lane_coords the seq kernel runs for this plan and tile (VAR_W; the tile's polynomial variable; the
 // tile's table slice, read where it lies), rebased on the box origins and packed.  A lane whose values do not fit an entry raises
-// `*overflow`: the plan then drops the table.
+// `*overflow`: the plan then drops the table.  `entry_bytes`: 12, or 8 -- the compact entry, whose K is the record's (`tap_s`: the plan's S).
 template <int VAR_W>
 __global__ __launch_bounds__(256) void k_fill_tap_table(const KernelCtx* ctxp, const TileBox* __restrict__ boxes, const TileBox* __restrict__ mboxes,
-                                                        int tiles_x, uint32_t* __restrict__ table, uint32_t* overflow)
+                                                        int tiles_x, uint32_t* __restrict__ table, uint32_t* overflow, int entry_bytes, int tap_s)
 {
     ctx_cref c = *(const V1C_CONST KernelCtx*)ctxp;
     ray_cref P = c.ray;
@@ -570,27 +595,49 @@ __global__ __launch_bounds__(256) void k_fill_tap_table(const KernelCtx* ctxp, c
         tc.y[k] = (int)((uint32_t)L.sy[k] - kRoundBias) - 32 * b.y0;
         tc.y2[k] = (int)((uint32_t)L.sy2[k] - kRoundBias) - 32 * q.y0;
     }
+    const size_t at = (size_t)t.box_tile * 256u + (size_t)tid;
+    if (entry_bytes == kTap8EntryBytes) {
+        const int K = tap_s - 32 * (b.y0 + q.y0);  // (mirror_rec_encode's expression)
+        if (!tap8_fits(tc, K))
+            atomicOr(overflow, 1u);
+        const TapEntry8 e = tap8_encode(tc, K);
+        uint32_t* out = table + at * 2u;
+        out[0] = e.w[0], out[1] = e.w[1];
+        return;
+    }
     if (!tap_entry_fits(tc))
         atomicOr(overflow, 1u);
     const TapEntry e = tap_entry_encode(tc);
-    uint32_t* out = table + ((size_t)t.box_tile * 256u + (size_t)tid) * 3u;
+    uint32_t* out = table + at * 3u;
     out[0] = e.w[0], out[1] = e.w[1], out[2] = e.w[2];
 }
 
-size_t tap_table_bytes(const Geom& g)
+size_t tap_table_bytes(const Geom& g, int entry_bytes)
 {
     const dim3 full = tile_grid(g, 256, 1);
-    return (size_t)full.x * (size_t)(full.y / 2 + 1) * (size_t)kTapSliceBytes;
+    return (size_t)full.x * (size_t)(full.y / 2 + 1) * 256u * (size_t)entry_bytes;
 }
 
-hipError_t launch_fill_tap_table(const KernelCtx& c, const KernelCtx* cdev, const void* boxes, const void* mboxes, void* table, uint32_t* overflow)
+int tap_table_s(const KernelCtx& c)
 {
+    const double s = 2.0 * c.ray.cy32;  // 64 x the row centre
+    return std::fabs(s) < 1.0e9 ? (int)std::llrint(s) : 0;
+}
+
+hipError_t launch_fill_tap_table(const KernelCtx& c, const KernelCtx* cdev, const void* boxes, const void* mboxes, void* table, uint32_t* overflow,
+                                 int entry_bytes)
+{
+    if (entry_bytes != kTapEntryBytes && entry_bytes != kTap8EntryBytes)
+        return hipErrorInvalidValue;
     const dim3 full = tile_grid(c.g, 256, 1);
     const dim3 grid(full.x, full.y / 2 + 1, 1), block(256, 1, 1);
+    const int tap_s = tap_table_s(c);
     if (c.ray.var_is_w)
-        hipLaunchKernelGGL((k_fill_tap_table<1>), grid, block, 0, 0, cdev, (const TileBox*)boxes, (const TileBox*)mboxes, (int)full.x, (uint32_t*)table, overflow);
+        hipLaunchKernelGGL((k_fill_tap_table<1>), grid, block, 0, 0, cdev, (const TileBox*)boxes, (const TileBox*)mboxes, (int)full.x, (uint32_t*)table, overflow,
+                           entry_bytes, tap_s);
     else
-        hipLaunchKernelGGL((k_fill_tap_table<0>), grid, block, 0, 0, cdev, (const TileBox*)boxes, (const TileBox*)mboxes, (int)full.x, (uint32_t*)table, overflow);
+        hipLaunchKernelGGL((k_fill_tap_table<0>), grid, block, 0, 0, cdev, (const TileBox*)boxes, (const TileBox*)mboxes, (int)full.x, (uint32_t*)table, overflow,
+                           entry_bytes, tap_s);
     return hipGetLastError();
 }
 
@@ -674,13 +721,14 @@ bool tile_mirror_rest(const void* host_boxes, const void* host_mboxes, const Geo
     return rest.size() <= (size_t)d.x * (TYh - 1) && rest.size() * 4 <= (size_t)d.x * d.y;
 }
 
-void tile_mirror_records(const void* host_boxes, const void* host_mboxes, size_t n_tiles, const Geom& g, int seq_kb, int one_kb, std::vector<char>& out)
+void tile_mirror_records(const void* host_boxes, const void* host_mboxes, size_t n_tiles, const Geom& g, int seq_kb, int one_kb, std::vector<char>& out,
+                         int tap_s)
 {
     const TileBox* b = (const TileBox*)host_boxes;
     const TileBox* q = (const TileBox*)host_mboxes;
     out.resize(n_tiles * sizeof(MirrorRecWords));
     for (size_t i = 0; i < n_tiles; i++) {
-        const MirrorRecWords w = mirror_rec_encode(b[i], q[i], seq_kb, one_kb, g.src_h, g.src_w);
+        const MirrorRecWords w = mirror_rec_encode(b[i], q[i], seq_kb, one_kb, g.src_h, g.src_w, tap_s);
         std::memcpy(&out[i * sizeof(MirrorRecWords)], &w, sizeof(w));
     }
 }
@@ -689,7 +737,7 @@ void tile_mirror_records(const void* host_boxes, const void* host_mboxes, size_t
 // seq_kb > 0 (pairs): k_ray_lin3_pair_mirror_seq, two box buffers of seq_kb KB, the eyes one after the other
 hipError_t launch_ray_lin3_pair_mirror(const KernelCtx& c, const KernelCtx* cdev, const LaunchUnits& lu, uint32_t* flags, const void* boxes,
                                        const void* mboxes, int half_dwords, int mirror_h, const uint32_t* rest_list, int n_rest, int raw_nwp,
-                                       hipStream_t stream, int seq_kb, const void* recs, const void* tap_table)
+                                       hipStream_t stream, int seq_kb, const void* recs, const void* tap_table, int tap_entry_bytes)
 {
     const int n_eyes = lu.n;
     const dim3 full = tile_grid(c.g, 256, 1);
@@ -765,9 +813,13 @@ hipError_t launch_ray_lin3_pair_mirror(const KernelCtx& c, const KernelCtx* cdev
             if (tab_off)
                 tap_table = nullptr;
 #endif
-            if (tap_table) {  // the plan's tap table in the head's table slot: the kernel that reads its coordinates (one instantiation)
-                hipLaunchKernelGGL(k_ray_lin3_pair_mirror_seq_tab, rgrid, block, slds, stream, head_pairs, a.tiles_x_magic, full.x, rows_strip, dst_wh,
-                                   (const double*)tap_table, a.ctx, (unsigned)a.kb | (unsigned)a.mirror_h << 16, a);
+            if (tap_table) {  // the plan's tap table in the head's table slot: the kernel that reads its coordinates, in the plan's entry form
+                if (tap_entry_bytes == kTap8EntryBytes)
+                    hipLaunchKernelGGL(k_ray_lin3_pair_mirror_seq_tab8, rgrid, block, slds, stream, head_pairs, a.tiles_x_magic, full.x, rows_strip, dst_wh,
+                                       (const double*)tap_table, a.ctx, (unsigned)a.kb | (unsigned)a.mirror_h << 16, a);
+                else
+                    hipLaunchKernelGGL(k_ray_lin3_pair_mirror_seq_tab, rgrid, block, slds, stream, head_pairs, a.tiles_x_magic, full.x, rows_strip, dst_wh,
+                                       (const double*)tap_table, a.ctx, (unsigned)a.kb | (unsigned)a.mirror_h << 16, a);
                 return hipGetLastError();
             }
             if (c.ray.var_is_w)

@@ -24,6 +24,7 @@
 #include "host_util.hpp"
 #include "kernels.hpp"
 #include "radial_fit.hpp"
+#include "tap_table.hpp"
 
 using namespace v1c;
 
@@ -204,8 +205,12 @@ static void border_for_depth(int depth, const double* bv, uint8_t cval8[4], floa
 // ------------------------------------------------------------------------------------------
 // plan
 // ------------------------------------------------------------------------------------------
-// no tap table (tap_table.hpp) above this size: a 4096 x 4096 pair plan holds 25.4 MB, a 16384 x 8192 one would hold 200
+// no tap table (tap_table.hpp) above this size: a 4096 x 4096 pair plan holds 16.9 MB (compact entries), a 16384 x 8192 one would hold 135
 static constexpr size_t kTapTableMaxBytes = (size_t)64 << 20;
+// The entry form, per plan: the compact 8-byte entry where the 12-byte table would pass this size, the 12-byte entry below it.  A large
+// table comes from HBM on every launch (the pixels the launch streams push it out of the Infinity Cache), so its bytes are paid in
+// full; a small one is re-read from cache between short launches, where the 12-byte entry's shorter decode is worth more than the bytes.
+static constexpr size_t kTapCompactMinBytes = (size_t)8 << 20;
 
 struct v1c_plan {
     int device = 0;
@@ -243,11 +248,12 @@ struct v1c_plan {
     // the mirror launch leaves to the pair kernel (k_ray_lin3_pair_mirror); mirror_boxes == nullptr: not used
     void* mirror_boxes = nullptr;
     const void* mirror_recs = nullptr;   // the same slots as launch records (tile_device.hpp: MirrorRec): what the seq / one-eye kernels read
-    // pairs without rest tiles: the lanes' tap coordinates, 12 bytes each (tap_table.hpp), filled at creation; nullptr: the plan has rest
+    // pairs without rest tiles: the lanes' tap coordinates, 12 or 8 bytes each (tap_table.hpp), filled at creation; nullptr: the plan has rest
     // tiles, the table would pass kTapTableMaxBytes, some lane's values do not fit an entry, or there was no memory for it -- every
     // launch then evaluates the map (one rule per plan: no launch mixes the two)
     const void* tap_table = nullptr;
     size_t tap_table_bytes = 0;
+    int tap_entry_bytes = 0;             // 12 or 8 (tap_table.hpp: TapEntry / TapEntry8, chosen by kTapCompactMinBytes); 0: no table
     const void* mirror_pairs = nullptr;  // tuning build: (tile box, band box) interleaved, 64 bytes per tile, for the kernels' A/B partners
     const uint32_t* mirror_rest = nullptr;
     int n_mirror_rest = 0;
@@ -834,7 +840,7 @@ extern "C" int v1c_plan_create_ex(v1c_plan** out, int device, const v1c_chain* c
 #endif
                             if (p->mirror_raw_nwp > 0) {  // the launch records of the seq / one-eye kernels: their prologue, done once
                                 std::vector<char> recs;
-                                tile_mirror_records(hb.data(), hm.data(), hb.size() / 32, g, p->mirror_seq_kb, p->mirror_raw_nwp, recs);
+                                tile_mirror_records(hb.data(), hm.data(), hb.size() / 32, g, p->mirror_seq_kb, p->mirror_raw_nwp, recs, tap_table_s(p->ctx));
                                 const char* dr = nullptr;
                                 if ((rc = upload(p, recs, &dr))) {
                                     v1c_plan_destroy(p);
@@ -843,15 +849,18 @@ extern "C" int v1c_plan_create_ex(v1c_plan** out, int device, const v1c_chain* c
                                 p->mirror_recs = dr;
                             }
                             // no rest tiles (C2: every tile pair fits the seq kernel's buffers): the lanes' coordinates, once per plan
-                            if (p->mirror_recs && p->mirror_seq_kb > 0 && mrest.empty() && tap_table_bytes(g) <= kTapTableMaxBytes) {
-                                const size_t tb = tap_table_bytes(g);
+                            int tap_form = tap_table_bytes(g, kTapEntryBytes) > kTapCompactMinBytes ? kTap8EntryBytes : kTapEntryBytes;
+                            if (const char* f = tuning_env("V1C_TAP_FORM"); f && (std::atoi(f) == kTapEntryBytes || std::atoi(f) == kTap8EntryBytes))
+                                tap_form = std::atoi(f);  // (A/B: one form at any size)
+                            if (p->mirror_recs && p->mirror_seq_kb > 0 && mrest.empty() && tap_table_bytes(g, tap_form) <= kTapTableMaxBytes) {
+                                const size_t tb = tap_table_bytes(g, tap_form);
                                 void* tt = nullptr;
                                 uint32_t over = 1;
                                 if (hipMalloc(&tt, tb + 16) == hipSuccess) {  // (the overflow word behind the entries)
                                     uint32_t* flag = (uint32_t*)((char*)tt + tb);
                                     hipError_t te = hipMemset(flag, 0, 16);
                                     if (te == hipSuccess)
-                                        te = launch_fill_tap_table(p->ctx, p->ctx_dev, p->tile_boxes, mbx, tt, flag);
+                                        te = launch_fill_tap_table(p->ctx, p->ctx_dev, p->tile_boxes, mbx, tt, flag, tap_form);
                                     if (te == hipSuccess)
                                         te = hipMemcpy(&over, flag, sizeof(over), hipMemcpyDeviceToHost);
                                     if (te != hipSuccess) {
@@ -860,14 +869,14 @@ extern "C" int v1c_plan_create_ex(v1c_plan** out, int device, const v1c_chain* c
                                         return fail(V1C_E_HIP, std::string("tap table: ") + hipGetErrorString(te));
                                     }
                                     if (over == 0)
-                                        p->allocs.push_back(tt), p->tap_table = tt, p->tap_table_bytes = tb;
+                                        p->allocs.push_back(tt), p->tap_table = tt, p->tap_table_bytes = tb, p->tap_entry_bytes = tap_form;
                                     else
                                         (void)hipFree(tt);
                                 } else {
                                     (void)hipGetLastError();  // (no memory for the table: the plan works without it)
                                 }
                                 if (const char* dbg = tuning_env("V1C_DEBUG"); dbg && dbg[0] == '1')
-                                    std::fprintf(stderr, "[v1c] tap table: %zu bytes, %s\n", tb, p->tap_table ? "in use" : "not kept");
+                                    std::fprintf(stderr, "[v1c] tap table: %zu bytes, %d per lane, %s\n", tb, tap_form, p->tap_table ? "in use" : "not kept");
                             }
                             std::vector<uint32_t> mrest1;
                             if (p->mirror_raw_nwp > 0 && tile_mirror_rest(hb.data(), hm.data(), g, p->half_dwords, g.dst_h, mrest1, p->mirror_raw_nwp, true, 1)) {
@@ -933,6 +942,11 @@ extern "C" int v1c_debug_read_stamps(v1c_plan* p, unsigned long long* out8)
 extern "C" int64_t v1c_plan_tap_table_bytes(const v1c_plan* p)
 {
     return p ? (int64_t)p->tap_table_bytes : 0;
+}
+
+extern "C" int v1c_plan_tap_entry_bytes(const v1c_plan* p)
+{
+    return p ? p->tap_entry_bytes : 0;
 }
 
 extern "C" int v1c_plan_path(const v1c_plan* p)
@@ -1211,7 +1225,7 @@ extern "C" int v1c_plan_run(v1c_plan* p, void* stream, const v1c_unit* units, in
             HIP_TRY(launch_ray_lin3_pair_mirror(p->ctx, p->ctx_dev, lu, flags, p->tile_boxes, p->mirror_raw_nwp > 0 ? p->mirror_pairs : p->mirror_boxes,
                                                 p->half_dwords, p->mirror_h,
                                                 n == 1 ? p->mirror_rest1 : p->mirror_rest, n == 1 ? p->n_mirror_rest1 : p->n_mirror_rest,
-                                                p->mirror_raw_nwp, st, p->mirror_seq_kb, p->mirror_recs, n == 2 ? p->tap_table : nullptr));
+                                                p->mirror_raw_nwp, st, p->mirror_seq_kb, p->mirror_recs, n == 2 ? p->tap_table : nullptr, p->tap_entry_bytes));
         } else if (d.fast && p->ctx.g.cn != 3) {
             // grayscale / BGRA: k_ray_lin_cn (one table entry per lane; plan-time boxes for the plan's own rotation, boxes reduced in the
             // kernel -- one unit per workgroup, a 12 KB buffer -- for units that override it)

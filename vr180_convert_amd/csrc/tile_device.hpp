@@ -2029,6 +2029,7 @@ struct MirrorRec {
     MirrorRecBox b, q;
     int idx0, nidx;   // the tile's table slice
     uint32_t flags;   // kMirrorRecMpoly: evaluate the polynomial in m; kMirrorRecFitSeq / FitOne: mirror_raw_fit(b, q, seq_kb / one_kb) == 1
+    int tap_k;        // tap_s - 32 * (b.y0 + q.y0): the K of the compact tap-table entry (tap_table.hpp), y2 = K - y + e
 };
 struct MirrorRecWords {
     uint32_t w[16];
@@ -2080,8 +2081,10 @@ __host__ __device__ inline MirrorRecBox mirror_rec_unbox(uint32_t w0, uint32_t w
     return r;
 }
 // `seq_kb`, `one_kb`: the box buffers of k_ray_lin3_pair_mirror_seq and of the one-eye k_ray_lin3_pair_mirror_raw for this plan (0: the
-// plan does not launch that kernel) -- the fit verdicts are the plan's, like the rest lists
-__host__ __device__ inline MirrorRecWords mirror_rec_encode(const TileBox& b, const TileBox& q, int seq_kb, int one_kb, int src_h, int src_w)
+// plan does not launch that kernel) -- the fit verdicts are the plan's, like the rest lists; `tap_s`: the plan's S of tap_table.hpp
+// (the nearest integer to 64 x the source's row centre), for the pairs the seq kernel serves
+__host__ __device__ inline MirrorRecWords mirror_rec_encode(const TileBox& b, const TileBox& q, int seq_kb, int one_kb, int src_h, int src_w,
+                                                            int tap_s = 0)
 {
     MirrorRecWords o;
     MirrorRecBox rb, rq;
@@ -2096,7 +2099,8 @@ __host__ __device__ inline MirrorRecWords mirror_rec_encode(const TileBox& b, co
     o.w[10] = fit ? (uint32_t)b.idx0 : 0u;
     o.w[11] = (fit ? (uint32_t)b.nidx : 1u) |
               (((b.interior & 2) ? kMirrorRecMpoly : 0u) | (fit_seq ? kMirrorRecFitSeq : 0u) | (fit_one ? kMirrorRecFitOne : 0u)) << 16;
-    o.w[12] = o.w[13] = o.w[14] = o.w[15] = 0u;
+    o.w[12] = fit_seq ? (uint32_t)(tap_s - 32 * (b.y0 + q.y0)) : 0u;
+    o.w[13] = o.w[14] = o.w[15] = 0u;
     return o;
 }
 __host__ __device__ inline MirrorRec mirror_rec_decode(const MirrorRecWords& v)
@@ -2105,6 +2109,7 @@ __host__ __device__ inline MirrorRec mirror_rec_decode(const MirrorRecWords& v)
     r.b = mirror_rec_unbox(v.w[0], v.w[1], v.w[2], v.w[3], v.w[4]);
     r.q = mirror_rec_unbox(v.w[5], v.w[6], v.w[7], v.w[8], v.w[9]);
     r.idx0 = (int)v.w[10], r.nidx = (int)(v.w[11] & 0xffffu), r.flags = v.w[11] >> 16;
+    r.tap_k = (int)v.w[12];
     return r;
 }
 __device__ __forceinline__ MirrorRec load_mirror_rec(const TileBox* pairs, int tile)

@@ -182,6 +182,14 @@ class Plan:
         f = getattr(_native.lib(), "v1c_plan_tap_table_bytes", None)
         return int(f(self._h)) if f is not None else 0
 
+    def tap_entry_bytes(self) -> int:
+        """Bytes per lane of that table (``v1c_plan_tap_entry_bytes``): 12, or 8 for the compact entry that plans with large tables
+        keep; 0 when the plan holds none.  A library behind ``V1C_LIB`` that predates the compact entry holds 12-byte entries."""
+        f = getattr(_native.lib(), "v1c_plan_tap_entry_bytes", None)
+        if f is None:
+            return 12 if self.tap_table_bytes() else 0
+        return int(f(self._h))
+
     def run(self, srcs: Sequence[torch.Tensor], dsts: Sequence[torch.Tensor], rots: Sequence[Any] | None = None) -> None:
         n = len(srcs)
         if n == 0 or len(dsts) != n or (rots is not None and len(rots) != n):
@@ -288,6 +296,11 @@ def last_tap_table_bytes() -> list[int]:
     """``Plan.tap_table_bytes`` per launch group of the calling thread's most recent ``remap_tensors`` / ``apply_lr_tensors`` call, in
     the order of ``last_launch_kinds`` (0: that plan evaluates its map in every launch; units served from a host map count 0)."""
     return [p.tap_table_bytes() if isinstance(p, Plan) else 0 for p in getattr(_TLS, "plans", [])]
+
+
+def last_tap_entry_bytes() -> list[int]:
+    """``Plan.tap_entry_bytes`` per launch group, in the order of ``last_tap_table_bytes`` (0: no table)."""
+    return [p.tap_entry_bytes() if isinstance(p, Plan) else 0 for p in getattr(_TLS, "plans", [])]
 
 
 def last_auto_radius_form() -> str:
