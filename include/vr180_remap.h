@@ -464,6 +464,48 @@ int v1c_color_match_luts_async(int device, void* stream, const void* left, int64
 int v1c_apply_luts_async(int device, void* stream, const void* src, int64_t src_pitch, void* dst, int64_t dst_pitch, int h, int w, int cn,
                          const uint8_t* luts_dev);
 
+/* ---- Lens vignetting: a radial gain over the image circle (INTEGRATION.md section 14 states the contract; tests/vignette_ref.py
+ * restates it).  Integer arithmetic from end to end; the only floating-point step is the host's sampling of the gain curve into the
+ * tables.  For the pixel (x, y) of an (h, w, cn) image of 8- or 16-bit elements (elem_bytes 1 / 2, maxv 255 / 65535):
+ *   r2  = (x - cx)^2 + (y - cy)^2, exact, in 64 bits                  (below 2^34: h, w <= 32767, -w <= cx < 2 w, -h <= cy < 2 h)
+ *   q   = (r2 * scale) >> shift, in unsigned 64 bits                   (0 < scale < 2^30, 0 <= shift <= 62)
+ *   idx = q >> 8, f = q & 255; where q >> 8 >= 1024: idx = 1023, f = 255 (the last interval is held)
+ *   G   = (T[idx] (256 - f) + T[idx + 1] f + 128) >> 8                (T: the channel's table, 1025 uint16 in Q14)
+ *   out = min(maxv, (v G + 2^13) >> 14)
+ * TABLES: 3 x 1025 uint16, in the order of a BGR pixel's channels.  A one-channel image takes the second (green) table; a fourth
+ * channel is copied.
+ * RINGS: over every pixel with r2 < R2 whose colour channels all lie in [lo, hi], ring = min(rings - 1, (r2 * rings) / R2): the
+ * channel's value is added to the ring's sum and 1 to its count.  The record is rings x 4 int64: sumB, sumG, sumR, n; a one-channel
+ * image fills sumG only.                                                                                                          */
+typedef struct v1c_vignette_geom {
+    int32_t cx, cy;         /* the circle's centre, pixels                                                                       */
+    uint32_t scale;         /* the table position's multiplier: about 256 * 1024 * 2^shift / radius^2                            */
+    int32_t shift;
+} v1c_vignette_geom;
+
+typedef struct v1c_vignette_ring_params {
+    int32_t cx, cy;         /* the circle's centre, pixels                                                                       */
+    int64_t r2;             /* R2: the circle's squared radius, 1 <= r2 < 2^35                                                    */
+    int32_t rings;          /* 16..1024, uniform in r2: equal areas                                                              */
+    int32_t lo, hi;         /* the mask, 0 <= lo <= hi <= maxv                                                                   */
+    int32_t reserved;       /* 0                                                                                                 */
+} v1c_vignette_ring_params;
+
+/* The gain pass of an (h, w, cn) device image; one launch on `stream`, no allocation, no copy, no synchronisation -- it can be
+ * captured into a graph.  dst may be src (in place) or another image that does not overlap it, with its own pitch.  tables_dev: the
+ * 3 x 1025 uint16 tables on the device; they may serve every frame of a shoot.  V1C_E_INVALID before any device call for NULL
+ * pointers, cn, elem_bytes, sizes outside 1..32767, a pitch below a row's bytes, pointers or pitches that are no multiple of
+ * elem_bytes, a centre further than one frame size outside the frame, scale or shift out of range.                                */
+int v1c_vignette_apply_async(int device, void* stream, const void* src, int64_t src_pitch, void* dst, int64_t dst_pitch, int h, int w,
+                             int cn, int elem_bytes, const v1c_vignette_geom* geom, const uint16_t* tables_dev);
+
+/* The ring statistics of an (h, w, cn) device image, on `stream`: the record zeroed by a launch, then one launch; no allocation, no
+ * copy to the host, no synchronisation -- it can be captured into a graph, and a replay starts from a zeroed record.  rings_dev:
+ * params->rings x 4 int64 on the device, 8-byte aligned; the sums are exact whatever the order of the adds.  The image is not written.
+ * V1C_E_INVALID as above, and for parameters out of range.                                                                        */
+int v1c_vignette_rings_async(int device, void* stream, const void* src, int64_t src_pitch, int h, int w, int cn, int elem_bytes,
+                             const v1c_vignette_ring_params* params, int64_t* rings_dev);
+
 /* ---- PNG encoding of a device image (INTEGRATION.md section 6 states the stream; tests/png_ref.py restates it) ------------------
  * The image's filtered scanlines, cut into bands of band_rows rows, every band deflated from an empty window as ONE dynamic Huffman
  * block of literals and distance-1 matches (zlib's Z_RLE class) closed by an empty stored block, or as stored blocks where that is

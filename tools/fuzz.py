@@ -7,7 +7,7 @@ and destination views (dword-aligned or not), per-unit rotations, apply_lr pairs
 (v1c_remap_lut) on random float32 maps sprinkled with NaN, infinities, 2^15 / 2^26 / 2^31-scale values and ties of the 1/32 grid.
 
     python3 tools/fuzz.py [--seconds 300] [--seed 1] [--big 0.15] [--lut 0.15] [--hot 0.3] [--gen2 0] [--api 0.1] [--auto 0.06] [--fused 0.06] [--log gpurun_out/fuzz.log]
-                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--jpegprog 0] [--jpegxc 0] [--jpegxf 0] [--jpegdmg 0] [--jpegodd 0] [--circle 0] [--colormatch 0] [--cases N]
+                          [--wide 0] [--png 0] [--jpeg 0] [--feat 0] [--jpegdec 0] [--jpegbatch 0] [--jpegopt 0] [--jpegprog 0] [--jpegxc 0] [--jpegxf 0] [--jpegdmg 0] [--jpegodd 0] [--circle 0] [--colormatch 0] [--vignette 0] [--cases N]
 
 --wide P: that share of the cases has uint16 or float32 pixels (k_remap_wide): the chain cases above -- same grammar, views, batches, pairs,
 per-unit rotations, graph replays and the same three masks, counted in the same counters -- and the LUT cases (v1c_remap_lut_ex, nothing left
@@ -42,7 +42,11 @@ with random off-centre center= values against oracle.remap of the host NumPy cha
 share goes through the colour match of two eyes (color_match_luts_tensor + apply_luts_tensor: random sizes with odd widths, channel
 counts, pitches, offsets, halves of a side-by-side buffer, modes, references, parameters off the defaults, in place and out of place,
 noise, flat frames, gradients and discs on black whose surrounds differ) against tests/colormatch_ref.py, byte for byte: histograms,
-tables, report, result and every byte of the buffer around the eyes.  These shares come off
+tables, report, result and every byte of the buffer around the eyes.  --vignette P: that share goes through the vignetting correction
+(vignette_rings_tensor + apply_vignette_tensor: random sizes, channel counts, uint8 / uint16, pitches, offsets, the right half of a
+side-by-side buffer, centres inside and up to one frame size outside the frame, radii from 1 px up, coefficients, gammas, ring counts,
+masks, in place and out of place) against tests/vignette_ref.py, byte for byte: the ring record, the result and every byte of the
+buffer around the image.  These shares come off
 the top of the case draw: with all of them at 0 every earlier seed replays as it ran.
 
 Round 5 added to the grammar: hot shapes of the chains that left the interpreter (planar fisheye -> fisheye, is_latitude_y=False, a
@@ -1512,6 +1516,55 @@ def colormatch_case(rng, dev) -> tuple[str, int]:
     return desc, bad
 
 
+VIGNETTE = {"drawn": 0}
+
+
+def vignette_case(rng, dev) -> tuple[str, int]:
+    """vignette_rings_tensor + apply_vignette_tensor against tests/vignette_ref.py, byte for byte: the ring record, the result and every
+    byte of the buffer around the image"""
+    import vignette_cases as VC
+    from vr180_convert_amd import vignette as VG
+
+    VIGNETTE["drawn"] += 1
+    h, w = (int(rng.integers(1, 200)), int(rng.integers(1, 300))) if rng.random() < 0.85 else (int(rng.integers(200, 900)), int(rng.integers(300, 1400)))
+    cn = int(rng.choice([1, 3, 4]))
+    dtype = np.uint8 if rng.random() < 0.5 else np.uint16
+    top = 255 if dtype == np.uint8 else 65535
+    kind = str(rng.choice(["noise", "noise", "flat", "gradient", "black", "white"]))
+    seed = int(rng.integers(0, 1 << 30))
+    if kind == "noise":
+        img = np.random.default_rng(seed).integers(0, top + 1, (h, w, cn)).astype(dtype)
+    elif kind == "gradient":
+        img = np.broadcast_to((np.arange(w) * top // max(1, w - 1)).astype(dtype)[None, :, None], (h, w, cn)).copy()
+    else:
+        img = np.full((h, w, cn), 0 if kind == "black" else top if kind == "white" else int(rng.integers(0, top + 1)), dtype)
+    center = (int(rng.integers(-w, 2 * w)), int(rng.integers(-h, 2 * h))) if rng.random() < 0.3 else (int(rng.integers(0, w)), int(rng.integers(0, h)))
+    radius = float(rng.choice([1.0, 2.0, 0.5 * max(h, w), 0.5 * min(h, w) + 0.5, rng.uniform(1.0, 3.0 * max(h, w))]))
+    k = lambda: (float(rng.uniform(-0.6, 0.3)), float(rng.uniform(-0.3, 0.3)), float(rng.uniform(-0.2, 0.2)))  # noqa: E731
+    coefs = ((k(), k(), k()), float(rng.choice([1.0, 1.0, 2.2, rng.uniform(0.5, 3.0)])))
+    if rng.random() < 0.1:
+        coefs = VC.IDENTITY
+    lo = int(rng.integers(0, top // 2))
+    hi = int(rng.integers(lo, top + 1))
+    if rng.random() < 0.5:
+        lo, hi = VG.default_mask(dtype)
+    es = np.dtype(dtype).itemsize
+    lay = dict(off=es * int(rng.integers(0, 17)), pad=es * int(rng.integers(0, 40)) if rng.random() < 0.5 else 0, sbs=bool(rng.random() < 0.4))
+    case = VC.carve(img, center=center, radius=radius, coefs=coefs, rings=int(rng.choice([16, 17, 64, 256, 1000, 1024])), lo=lo, hi=hi,
+                    inplace=bool(rng.random() < 0.5), **lay)
+    desc = (f"vignette {kind} {np.dtype(dtype).name} {h}x{w}x{cn} {lay} centre {center} radius {radius:.3f} rings {case.rings} mask [{lo}, {hi}] "
+            f"inplace {case.inplace} {coefs}")
+    base_t = torch.from_numpy(case.base.copy()).to(dev)
+    typed = base_t if es == 1 else base_t[: base_t.numel() // 2 * 2].view(torch.uint16)
+    image = torch.as_strided(typed, (h, w, cn), (case.pitch // es, cn, 1), case.off // es)
+    rec = VG.vignette_rings_tensor(image, center=center, radius=radius, rings=case.rings, lo=lo, hi=hi)
+    out = VG.apply_vignette_tensor(image, case.vignette(), center=center, radius=radius, out=image if case.inplace else None)
+    wres, wrec = VC.reference_of(case)
+    bad = int((rec.cpu().numpy() != wrec).sum()) + int((out.cpu().numpy() != wres).sum())
+    bad += int((base_t.cpu().numpy() != VC.expected_base(case, wres)).sum())
+    return desc, bad
+
+
 def circle_remap_case(rng, dev) -> tuple[str, int]:
     h, w = int(rng.integers(24, 700)), int(rng.integers(24, 700))
     wo, ho = int(rng.integers(8, 600)), int(rng.integers(8, 600))
@@ -1780,6 +1833,7 @@ def main() -> int:
     ap.add_argument("--jpegodd", type=float, default=0.0, help="share of cases through the device JPEG decoders with a legal file of unusual structure or one damaged header, against tests/jpgodd_cases.py")
     ap.add_argument("--circle", type=float, default=0.0, help="share of cases through the image-circle fit (v1c_fit_circle) against circle_ref.fit, a part of them remaps with random off-centre center= against the oracle")
     ap.add_argument("--colormatch", type=float, default=0.0, help="share of cases through the colour match of two eyes (color_match_luts_tensor, apply_luts_tensor) against colormatch_ref, byte for byte")
+    ap.add_argument("--vignette", type=float, default=0.0, help="share of cases through the vignetting correction (vignette_rings_tensor, apply_vignette_tensor) against vignette_ref, byte for byte")
     ap.add_argument("--chroma", type=float, default=0.0, help="share of the remap (chain) cases that draw a ChromaticAberration (remap_tensors(chromatic=)) and are held to the per-channel oracle composition")
     ap.add_argument("--cases", type=int, default=None, help="stop after this many cases (before --seconds runs out)")
     ap.add_argument("--feat", type=float, default=0.0, help="share of cases through the feature pipeline (features.detect / features.match) against tests/feat_ref.py")
@@ -1815,13 +1869,16 @@ def main() -> int:
             r_kind = rng.random()
             wide_chain = False
             counted = True
-            rest0000 = 1.0 - a.colormatch
+            rest00000 = 1.0 - a.vignette
+            rest0000 = rest00000 - a.colormatch
             rest000 = rest0000 - a.circle
             rest00 = rest000 - a.jpegodd
             rest0 = rest00 - a.jpegdmg
             rest = rest0 - a.jpegxf
             top = rest - a.jpegxc - a.jpegprog - a.jpegopt - a.jpegbatch - a.jpegdec
-            if r_kind >= rest0000:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+            if r_kind >= rest00000:  # (the new shares come off the top: with all of them at 0 every earlier seed replays as it ran)
+                desc, bad = vignette_case(rng, dev)
+            elif r_kind >= rest0000:
                 desc, bad = colormatch_case(rng, dev)
             elif r_kind >= rest000:
                 desc, bad = circle_case(rng, dev)
@@ -1898,6 +1955,7 @@ def main() -> int:
            if ODD["drawn"] else "")
         + (f"; circle cases: {CIRCLE['drawn']} drawn" if CIRCLE["drawn"] else "")
         + (f"; colormatch cases: {COLORMATCH['drawn']} drawn" if COLORMATCH["drawn"] else "")
+        + (f"; vignette cases: {VIGNETTE['drawn']} drawn" if VIGNETTE["drawn"] else "")
         + (f"; chroma cases: {CHROMA['drawn']} drawn, {CHROMA['fixup']} with a fix-up pass, {CHROMA['literal']} on the literal path" if CHROMA["drawn"] else ""))
     say("kernel families of the chain cases' launch groups: " + ", ".join(f"{k} x{v}" for k, v in sorted(KINDS.items())))
     return 1 if n_bad else 0

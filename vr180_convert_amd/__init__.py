@@ -29,6 +29,7 @@ from .jpeg_compose_device import (compose_regions, join_sbs_jpeg, normalize_orie
 from .sharding import remap_sharded
 from .circle import Circle, fit_circle, fit_circle_tensor
 
+_VIGNETTE = ("Vignette", "gain_tables", "apply_vignette_tensor", "vignette_rings_tensor", "fit_vignette")
 _COLORMATCH = ("color_match_luts_tensor", "apply_luts_tensor", "match_eyes_tensors", "color_match_report", "ColorMatchReport")
 
 
@@ -42,6 +43,10 @@ def __getattr__(name: str):
         from . import chromatic
 
         return chromatic.ChromaticAberration
+    if name in _VIGNETTE:  # (and a remap without vignette= imports none of vignette.py)
+        from . import vignette
+
+        return getattr(vignette, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -111,4 +116,10 @@ __all__ = [
     "ColorMatchReport",
     # lateral chromatic aberration corrected inside the remap, one map per colour channel (chromatic= / --chromatic)
     "ChromaticAberration",
+    # lens vignetting corrected by a radial gain in front of the remap, and fitted from a flat-field frame (vignette= / --vignette)
+    "Vignette",
+    "gain_tables",
+    "apply_vignette_tensor",
+    "vignette_rings_tensor",
+    "fit_vignette",
 ]

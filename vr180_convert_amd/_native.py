@@ -34,6 +34,7 @@ SYMBOLS = [
     "v1c_color_match_workspace", "v1c_color_match_luts_async", "v1c_apply_luts_async",
     "v1c_plan_tap_table_bytes", "v1c_plan_tap_entry_bytes",
     "v1c_ca_plan_create", "v1c_ca_plan_run", "v1c_ca_plan_get_map", "v1c_ca_plan_path", "v1c_ca_plan_last_launch", "v1c_ca_plan_destroy",
+    "v1c_vignette_apply_async", "v1c_vignette_rings_async",
 ]
 
 
@@ -166,6 +167,11 @@ def lib() -> C.CDLL:
         L.v1c_ca_plan_path.argtypes = [vp]
         L.v1c_ca_plan_last_launch.argtypes = [vp]
         L.v1c_ca_plan_destroy.argtypes = [vp]
+    except AttributeError:  # (an older build behind V1C_LIB)
+        pass
+    try:
+        L.v1c_vignette_apply_async.argtypes = [i32, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp, vp]
+        L.v1c_vignette_rings_async.argtypes = [i32, vp, vp, i64, i32, i32, i32, i32, vp, vp]
     except AttributeError:  # (an older build behind V1C_LIB)
         pass
     try:

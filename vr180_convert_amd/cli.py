@@ -111,6 +111,25 @@ def parse_chromatic(text: str, *, pair: bool = True, swap: bool = False) -> Any:
     return ca
 
 
+def parse_vignette(text: str, gamma: float = 1.0, *, pair: bool = True, swap: bool = False) -> Any:
+    """``--vignette``: '' -> None, 'k1,k2,k3' or 'b:k1,k2,k3;g:...;r:...' -> a Vignette (V = 1 + k1 rho^2 + k2 rho^4 + k3 rho^6, 1.0 = the
+    rim of the image circle) with ``--vignette-gamma``, and for a pair of eyes 'LEFT|RIGHT' -> one per eye, which ``swap`` exchanges with
+    the eyes"""
+    if text == "":
+        return None
+    from . import vignette
+
+    try:
+        if not pair and "|" in text:
+            raise ValueError("one correction for every image: no per-eye 'LEFT|RIGHT' form here")
+        v = vignette.parse_pair(text, gamma) if pair else vignette.parse(text, gamma)
+    except ValueError as e:
+        raise typer.BadParameter(f"--vignette {text} (--vignette-gamma {gamma}): {e}") from e
+    if isinstance(v, tuple) and swap:
+        return (v[1], v[0])
+    return v
+
+
 def closest_in_time(directory: Path, anchor: Path, offset_s: float) -> Path:
     """The file under ``directory`` (recursively) with ``anchor``'s suffix whose modification time is closest to
     ``anchor``'s, shifted by ``offset_s`` seconds (cli.py:178-216)."""
@@ -281,11 +300,19 @@ def lr(
                                                                 "'r:c0,c1,...;b:c0,c1,...' -- per channel a polynomial in the normalised "
                                                                 "source radius (1.0 = the rim), lowest order first; 'LEFT|RIGHT' for one "
                                                                 "per eye (swapped by --swap); 8-bit BGR images; default: off")] = "",
+    vignette: Annotated[str, typer.Option("--vignette", help="Correct lens vignetting on the GPU in front of the remap: 'k1,k2,k3' of "
+                                                              "V = 1 + k1 r^2 + k2 r^4 + k3 r^6 (r = 1.0 at the rim), "
+                                                              "'b:..;g:..;r:..' per channel, 'LEFT|RIGHT' for one per eye (swapped by "
+                                                              "--swap); 8- and 16-bit images; the `vignette` command fits them; "
+                                                              "default: off")] = "",
+    vignette_gamma: Annotated[float, typer.Option("--vignette-gamma", help="With --vignette: the power-law encoding of the pixels, 1.0 for "
+                                                                           "linear light, 2.2 for the usual 8-bit files")] = 1.0,
 ) -> None:
     """Remap a pair of fisheye images to a pair of SBS equirectangular images."""
     from .remapper import apply_lr
 
     chromatic_ = parse_chromatic(chromatic, swap=swap)
+    vignette_ = parse_vignette(vignette, vignette_gamma, swap=swap)
 
     if match_colors not in ("", "gain", "histogram"):
         raise typer.BadParameter(f"--match-colors {match_colors}: expected 'gain' or 'histogram'")
@@ -335,7 +362,8 @@ def lr(
              **({"device_jpeg_optimize": True} if device_jpeg_optimize else {}),
              **({"device_decode_progressive": True} if device_decode_progressive else {}),
              **({"match_colors": match_colors, "match_reference": match_reference} if match_colors else {}),
-             **({} if chromatic_ is None else {"chromatic": chromatic_}))
+             **({} if chromatic_ is None else {"chromatic": chromatic_}),
+             **({} if vignette_ is None else {"vignette": vignette_}))
 
 
 @app.command()
@@ -370,11 +398,17 @@ def s(
                                                                 "'r:c0,c1,...;b:c0,c1,...' -- per channel a polynomial in the normalised "
                                                                 "source radius (1.0 = the rim), lowest order first; 8-bit BGR images; "
                                                                 "default: off")] = "",
+    vignette: Annotated[str, typer.Option("--vignette", help="Correct lens vignetting on the GPU in front of the remap: 'k1,k2,k3' of "
+                                                              "V = 1 + k1 r^2 + k2 r^4 + k3 r^6 (r = 1.0 at the rim) or "
+                                                              "'b:..;g:..;r:..' per channel; 8- and 16-bit images; default: off")] = "",
+    vignette_gamma: Annotated[float, typer.Option("--vignette-gamma", help="With --vignette: the power-law encoding of the pixels, 1.0 for "
+                                                                           "linear light, 2.2 for the usual 8-bit files")] = 1.0,
 ) -> None:
     """Remap fisheye images to equirectangular images (one shared map for all of them)."""
     from .remapper import apply
 
     chromatic_ = parse_chromatic(chromatic, pair=False)
+    vignette_ = parse_vignette(vignette, vignette_gamma, pair=False)
 
     if out_path == Path(""):
         out_paths = [p.with_suffix(f".out.{DEFAULT_EXTENSION}") for p in in_paths]
@@ -392,7 +426,30 @@ def s(
           **({"device_decode": "batch"} if device_decode_batch else {"device_decode": True} if device_decode else {}),
           **({"device_jpeg_optimize": True} if device_jpeg_optimize else {}),
           **({"device_decode_progressive": True} if device_decode_progressive else {}),
-          **({} if chromatic_ is None else {"chromatic": chromatic_}))
+          **({} if chromatic_ is None else {"chromatic": chromatic_}),
+          **({} if vignette_ is None else {"vignette": vignette_}))
+
+
+@app.command(name="vignette")
+def vignette_fit(
+    flat_path: Annotated[Path, typer.Argument(help="A flat-field frame of the lens: a white wall, an overcast sky, a diffuser over the lens")],
+    center: Annotated[str, typer.Option(help="Centre of the image circle in source pixels: 'auto' (fitted) or 'X,Y'; default: the frame's "
+                                             "centre")] = "",
+    radius: Annotated[str, typer.Option(help="Radius of the image circle: a number or 'fit' (the fitted image circle's)")] = "fit",
+    rings: Annotated[int, typer.Option(help="Rings of equal area the statistics are gathered in, 16..1024")] = 256,
+    gamma: Annotated[float, typer.Option(help="The power-law encoding of the frame's pixels: 1.0 for linear light, 2.2 for the usual 8-bit "
+                                              "files; pass the same value as --vignette-gamma")] = 1.0,
+) -> None:
+    """Fit the vignetting of a lens from a flat-field frame on the GPU and print the coefficients in the form --vignette reads."""
+    from . import vignette
+
+    radius_: Any = "fit" if radius == "fit" else float(radius)
+    center_: Any = None if center == "" else parse_center(center, pair=False)
+    try:
+        v = vignette.fit_vignette(_io.imread(flat_path), center=center_, radius=radius_, rings=rings, gamma=gamma)
+    except ValueError as e:
+        raise typer.BadParameter(str(e)) from e
+    typer.echo(v.spec())
 
 
 @app.command()

@@ -322,6 +322,9 @@ def clear_caches() -> None:
     ca = sys.modules.get(__package__ + ".chromatic")  # (its plans too, when the module was ever used)
     if ca is not None:
         ca.clear_caches()
+    vg = sys.modules.get(__package__ + ".vignette")  # (and its tables on the device)
+    if vg is not None:
+        vg._TABLES.clear()
 
 
 def _plan_for(chain: _abi.Chain, *, src_hw, dst_wh, cn, interpolation, border_mode, border_value, device,
@@ -474,6 +477,7 @@ def remap_tensors(
     rotations: Sequence[Any] | None = None,
     center: Any = None,
     chromatic: Any = None,
+    vignette: Any = None,
 ) -> list[str]:
     """Device-resident core of ``apply``: remap every ``srcs[k]`` into ``dsts[k]`` (same device,
     same shapes) on the current stream.  ``transformer`` is one chain shared by all units
@@ -487,6 +491,9 @@ def remap_tensors(
     map per colour channel: channel ``c`` of every result is channel ``c`` of what this call gives for ``transformer *
     PolynomialScaler(coefs_c)``.  uint8 BGR images and lowerable chains only: ValueError (not 3-channel), TypeError (uint16 / float32),
     NotImplementedError (a chain that cannot be lowered), before anything is launched.  ``None``: nothing of it runs.
+    ``vignette``: a ``vignette.Vignette`` (or one per unit) -- every source is multiplied by the lens's radial gain in front of the remap
+    (and so in front of ``chromatic``), into a temporary: the caller's tensors stay as they are.  The circle is the remap's: this
+    ``radius`` and ``center``.  One more launch per source; uint8 and uint16 images (TypeError otherwise, before anything is launched).
     Returns the code path used per launch group ('ray' / 'literal' / 'lut').  Nothing is
     synchronised (``center="auto"`` synchronises once per source)."""
     n = len(srcs)
@@ -496,9 +503,17 @@ def remap_tensors(
         from . import chromatic as _ca
 
         _ca.check_images(list(srcs) + list(dsts))
+    if vignette is not None:
+        from . import vignette as _vg
+
+        _vg.as_per_unit(vignette, n)
+        for s_ in srcs:
+            _vg.check_dtype(s_.dtype)
     centers = None
     if center is not None:
         centers = per_unit_centers(fit_centers(center, srcs) if isinstance(center, str) else center, n)
+    if vignette is not None:
+        srcs = _vg.correct_sources(srcs, vignette, centers=centers, radius=radius)
     if chromatic is not None:
         paths, _TLS.plans = _ca.remap_tensors_chromatic(transformer, srcs, dsts, chromatic, radius=radius, interpolation=interpolation,
                                                         boarder_mode=boarder_mode, boarder_value=boarder_value, size_input=size_input,
@@ -845,6 +860,7 @@ def apply(
     device_decode_progressive: bool = False,
     center: Any = None,
     chromatic: Any = None,
+    vignette: Any = None,
 ) -> Sequence[NDArray[np.uint8]]:
     """Apply transformer to images (reference remapper.py:324-403).
 
@@ -872,13 +888,18 @@ def apply(
     radius (``get_radius_smart``); the radius stays shared, the maximum over the images, whatever the centres.
 
     ``chromatic``: a ``chromatic.ChromaticAberration`` -- lateral chromatic aberration corrected inside the remap, one map per colour
-    channel (``remap_tensors``); uint8 BGR images and lowerable chains only, refused before anything is launched."""
+    channel (``remap_tensors``); uint8 BGR images and lowerable chains only, refused before anything is launched.
+
+    ``vignette``: one ``vignette.Vignette`` -- every image is multiplied by the lens's radial gain in front of the remap, with the
+    remap's circle (``radius``, ``center``); arrays and tensors of the caller's stay as they are, images this call read or decoded
+    itself are corrected where they lie.  uint8 and uint16 images, TypeError otherwise, before anything is launched."""
     device_jpeg = _device_jpeg_mode(device_jpeg)
     jpeg_kw = {"optimize": True} if device_jpeg_optimize else {}
     in_paths_ = [in_paths] if isinstance(in_paths, (str, Path, np.ndarray, torch.Tensor)) else in_paths
     out_paths_ = [out_paths] if isinstance(out_paths, (str, Path)) else out_paths
     del in_paths, out_paths
 
+    caller_items = list(in_paths_)
     if device_decode:
         in_paths_ = _decode_on_device(list(in_paths_), device, device_decode, device_decode_progressive)
     images = _io.imread_many(list(in_paths_))
@@ -894,6 +915,13 @@ def apply(
             raise TypeError(f"apply: chromatic must be one ChromaticAberration, not {chromatic!r}")
         _ca.check_images(images)
         ca_kw = {"chromatic": chromatic}
+    if vignette is not None:
+        from . import vignette as _vg
+
+        if not isinstance(vignette, _vg.Vignette):  # (one map serves every image: one correction)
+            raise TypeError(f"apply: vignette must be one Vignette, not {vignette!r}")
+        for im in images:
+            _vg.check_dtype(im.dtype)
     fits = None
     if (isinstance(radius, str) and radius == "fit") or isinstance(center, str):
         if isinstance(center, str) and _capturing():
@@ -918,7 +946,8 @@ def apply(
 
         def _group(srcs_g, dsts_g):
             remap_tensors(transformer, srcs_g, dsts_g, radius=radius_, interpolation=interpolation, boarder_mode=boarder_mode,
-                          boarder_value=boarder_value, size_input=size_in, center=center_, **ca_kw)
+                          boarder_value=boarder_value, size_input=size_in, center=center_, **ca_kw,
+                          **({} if vignette is None else {"vignette": vignette}))
 
         results = _hostpipe.run(imgs3, dev, (size_output[1], size_output[0], int(imgs3[0].shape[2])), _group)
         results = [r[..., 0] if a.ndim == 2 else r for r, a in zip(results, host_imgs)]
@@ -927,6 +956,9 @@ def apply(
         return results
 
     srcs = [_to_device(im, dev) for im in images]
+    if vignette is not None:  # (in place where the tensor is this call's own: an upload or a decode; never in the caller's)
+        srcs = _vg.correct_sources(srcs, vignette, centers=centers, radius=radius_,
+                                   inplace=[not isinstance(q, torch.Tensor) for q in caller_items])
     cn = srcs[0].shape[2]
     dsts = [torch.empty((size_output[1], size_output[0], cn), dtype=s.dtype, device=dev) for s in srcs]
     if boarder_mode == _abi.BORDER_TRANSPARENT:
@@ -1084,6 +1116,7 @@ def apply_lr_tensors(
     match_colors: Literal["gain", "histogram"] | None = None,
     match_reference: Literal["left", "right"] = "left",
     chromatic: Any = None,
+    vignette: Any = None,
 ) -> torch.Tensor:
     """Device-resident ``apply_lr`` (merge=False): both eyes are remapped by ONE launch straight
     into the halves of the ``(H, 2W, C)`` side-by-side tensor (remapper.py:460-484, 517-518).
@@ -1112,7 +1145,17 @@ def apply_lr_tensors(
     ``chromatic``: a ``chromatic.ChromaticAberration`` for both eyes -- one launch of two units -- or ``(left, right)``, one per eye: two
     plans.  Lateral chromatic aberration corrected inside the remap, one map per colour channel (``remap_tensors``).  uint8 BGR eyes and
     lowerable chains only; ``radius="auto"`` takes its exact form (``auto_radius_on_device=True``: NotImplementedError).  All refused
+    before anything is launched.  None: nothing of it runs.
+
+    ``vignette``: a ``vignette.Vignette`` for both eyes or ``(left, right)``, one per eye -- each eye is multiplied by its lens's radial
+    gain in front of the remap (and so in front of ``chromatic`` and ``match_colors``), into a temporary: the caller's tensors stay as
+    they are.  The circle is the remap's: ``center`` (``"auto"`` included) and ``radius`` -- a number, ``"max"``, ``"fit"`` or the
+    exact form of ``"auto"``, resolved ONCE, on the eyes as they came, and used by both (``auto_radius_on_device=True``: the radius
+    never reaches the host, NotImplementedError).  One more launch per eye; uint8 and uint16 eyes, TypeError otherwise; all refused
     before anything is launched.  None: nothing of it runs."""
+    if vignette is not None:
+        left, right, radius, center = _vignette_pair(transformer, left, right, vignette, radius=radius, center=center,
+                                                     auto_radius_on_device=auto_radius_on_device)
     ca_kw: dict = {}
     if chromatic is not None:
         from . import chromatic as _ca
@@ -1179,8 +1222,9 @@ def apply_lr_tensors(
         _TLS.auto_form = "exact"
     if isinstance(transformer, tuple):
         # per-eye transformer AND per-eye radius estimate (remapper.py:460-473)
-        r = [get_radius_smart(radius, [im]) if fits is None else get_radius_smart(radius, [im], fits=[f])
-             for im, f in zip((left, right), fits or (None, None))]
+        r = list(radius) if isinstance(radius, tuple) else [
+            get_radius_smart(radius, [im]) if fits is None else get_radius_smart(radius, [im], fits=[f])
+            for im, f in zip((left, right), fits or (None, None))]  # (a tuple: what _vignette_pair resolved per eye)
         if r[0] == r[1]:
             remap_tensors(list(transformer), [left, right], halves, radius=r[0], interpolation=interpolation,
                           boarder_mode=boarder_mode, boarder_value=boarder_value, center=centers, **ca_kw)
@@ -1201,6 +1245,37 @@ def apply_lr_tensors(
             remap_tensors(transformer, [left, right], halves, radius=r_, interpolation=interpolation,
                           boarder_mode=boarder_mode, boarder_value=boarder_value, size_input=size_in)
     return out
+
+
+def _vignette_pair(transformer, left, right, vignette, *, radius, center, auto_radius_on_device=None, inplace=(False, False)):
+    """``vignette=`` of the pair entries: the circle resolved as the remap resolves it -- once, on the eyes as they came --, both eyes
+    corrected (vignette.py; ``inplace[k]``: where eye k lies), and what the remap is then called with: ``(left, right, radius,
+    center)``.  ``radius`` comes back as a number, or as ``(r_left, r_right)`` where a transformer per eye takes a radius per eye."""
+    from . import vignette as _vg
+
+    vs = _vg.as_per_unit(vignette, 2)
+    for im in (left, right):
+        _vg.check_dtype(im.dtype)
+    if auto_radius_on_device:
+        raise NotImplementedError("vignette: with auto_radius_on_device=True the radius never reaches the host, where the gain's geometry "
+                                  "is made; pass auto_radius_on_device=None (the exact form) or a numeric radius")
+    fits = None
+    if isinstance(center, str):
+        fits = None if _capturing() else fit_circles([left, right])
+        center = fit_centers(center, [left, right], fits=fits)
+    elif isinstance(radius, str) and radius == "fit":
+        fits = fit_circles([left, right])
+    centers = per_unit_centers(center, 2)
+    if isinstance(radius, str) and radius == "auto":
+        _TLS.auto_form = "exact"
+    if isinstance(transformer, tuple):  # per-eye transformer AND per-eye radius (remapper.py:460-473)
+        r = [get_radius_smart(radius, [im]) if fits is None else get_radius_smart(radius, [im], fits=[f])
+             for im, f in zip((left, right), fits or (None, None))]
+    else:
+        r = [get_radius_smart(radius, [left, right]) if fits is None else get_radius_smart(radius, [left, right], fits=fits)] * 2
+    eyes = [_vg.correct_sources([im], v, centers=None if centers is None else [centers[k]], radius=r[k], inplace=inplace[k])[0]
+            for k, (im, v) in enumerate(zip((left, right), vs))]
+    return eyes[0], eyes[1], (r[0] if r[0] == r[1] else (r[0], r[1])), center
 
 
 def _check_match_colors(match_colors: Any, match_reference: Any, left: Any, right: Any) -> None:
@@ -1254,6 +1329,7 @@ def apply_lr(
     match_colors: Literal["gain", "histogram"] | None = None,
     match_reference: Literal["left", "right"] = "left",
     chromatic: Any = None,
+    vignette: Any = None,
 ) -> None:
     """Apply transformer to a pair of images and save them side by side (reference
     remapper.py:406-520).  ``left_path == right_path`` means one file holding both eyes.
@@ -1280,7 +1356,10 @@ def apply_lr(
     remapped.  Where the result comes to the host anyway, a match that ended in a status (too few pixels in the mask) is logged as a
     warning; the device writers leave the report on the device.
     ``chromatic``: as in ``apply_lr_tensors`` -- a ``chromatic.ChromaticAberration`` or ``(left, right)``; the remap's result is what
-    ``match_colors``, ``merge`` and every writer then see."""
+    ``match_colors``, ``merge`` and every writer then see.
+    ``vignette``: as in ``apply_lr_tensors`` -- a ``vignette.Vignette`` or ``(left, right)``: the lens's radial gain on each eye in front
+    of the remap.  Arrays and tensors of the caller's stay as they are; eyes this call read or decoded itself are corrected where they
+    lie."""
     vr180 = isinstance(device_jpeg, str) and device_jpeg == "vr180"
     device_jpeg = True if vr180 else _device_jpeg_mode(device_jpeg)
     if vr180 and merge:
@@ -1288,6 +1367,7 @@ def apply_lr(
     if vr180 and not (isinstance(out_path, (str, Path)) and Path(out_path).suffix.lower() in (".jpg", ".jpeg")):
         raise ValueError(f'device_jpeg="vr180" takes a .jpg / .jpeg out_path, not {out_path}')  # (before anything is read or remapped)
     jpeg_kw = {"optimize": True} if device_jpeg_optimize else {}
+    caller_left, caller_right = left_path, right_path
     if device_decode:
         if isinstance(left_path, (str, Path)) and isinstance(right_path, (str, Path)) and left_path == right_path:
             both = _decode_on_device([left_path], device, device_decode, device_decode_progressive)[0]
@@ -1307,15 +1387,24 @@ def apply_lr(
         _ca.as_per_unit(chromatic, 2)
         _ca.check_images([left, right])
         ca_kw = {"chromatic": chromatic}
+    if vignette is not None:  # (likewise)
+        from . import vignette as _vg
+
+        _vg.as_per_unit(vignette, 2)
+        for im in (left, right):
+            _vg.check_dtype(im.dtype)
     on_device = isinstance(left, torch.Tensor) and left.is_cuda
     dev = left.device if on_device else _device(device)
     if match_colors is not None:
         _check_match_colors(match_colors, match_reference, left, right)
     lt, rt = _to_device(left, dev), _to_device(right, dev)
     # "auto" radius: estimated on the host images when they are numpy (one row each)
+    radius_ = _radius_for_pair(radius, transformer, left, right)
+    if vignette is not None:  # (in place where the eye is this call's own: an upload, or a decode the caller never sees)
+        own = [not isinstance(q, torch.Tensor) for q in (caller_left, caller_right)]
+        lt, rt, radius_, center = _vignette_pair(transformer, lt, rt, vignette, radius=radius_, center=center, inplace=own)
     sbs = apply_lr_tensors(transformer, lt, rt, size_output=size_output, interpolation=interpolation,
-                           boarder_mode=boarder_mode, boarder_value=boarder_value,
-                           radius=_radius_for_pair(radius, transformer, left, right), center=center, **ca_kw)
+                           boarder_mode=boarder_mode, boarder_value=boarder_value, radius=radius_, center=center, **ca_kw)
     match_report = _match_sbs_colors(sbs, size_output[0], match_colors, match_reference) if match_colors is not None else None
     if merge and sbs.dtype != torch.uint8:
         # 16-bit / float32: the reference's own NumPy expression (remapper.py:485-497) on the host copy (the anaglyph kernel is 8-bit)
